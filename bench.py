@@ -11,6 +11,10 @@ task descriptors already resident in HBM. Inside the timed region, per step:
 Host-side descriptor building / interning (what the Go shim does while it enqueues tasks) is
 outside the timed region; its cost and the PCIe-inclusive rate are reported in DESIGN.md.
 
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds what takes runs of its own: the
+end-to-end runs outside the timed region (`end_to_end`) and the CPU oracle baseline (`cpu_baseline`, unless
+--no-cpu-baseline). `--dump-outputs DIR` writes what the last timed step computed (the placements) as DIR/<name>.npy.
+
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); see DESIGN.md "Multi-GPU".
 """
 import argparse
@@ -43,6 +47,26 @@ def emit_line(text):
         pass
     sys.stdout.flush()
     os.write(1, (text + "\n").encode())
+
+
+DUMP_BUDGET_B = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: the arrays a caller of the timed path received from its last step, one DIR/<name>.npy each, in float64.
+    Beyond DUMP_BUDGET_B in all, every array is cut to a fixed, seeded sample of its rows (sorted), written with the rows it kept
+    as DIR/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_B and a.ndim > 0 and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_BUDGET_B / total / 2))   # (half of the budget each for the sample and its row numbers)
+            rows = np.sort(np.random.default_rng(0x5EED).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def profile_traffic(kernel, run=None):
@@ -197,6 +221,8 @@ def run_sharded(args, ranks, wl, eng, sched, descs, ranges, t_host_prep):
         n_ptasks += st["propose_tasks"]
     sync()
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"placements": out})
     device_rounds = device_rounds and not state["host_merge"]   # (what really ran: the labels below follow it)
     K = max(args.steps, 1)
     t_step = elapsed / K
@@ -247,7 +273,7 @@ def run_sharded(args, ranks, wl, eng, sched, descs, ranges, t_host_prep):
         # curve points DOWN at every size one GPU holds.
         "expected_speedup": "<1 below ~650k nodes",
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(wl)
     if rank == 0:
         emit_line(json.dumps(result))
@@ -372,6 +398,8 @@ def run_churn(args, ranks, wl, eng, descs, ranges):
         torch.cuda.synchronize()
         ranks.barrier()
     tt = ranks.max_over_ranks(sum(t_rounds)) if by_rank else sum(t_rounds)
+    if args.dump_outputs and rank == 0:   # (the node of every task of the workload after the last round)
+        dump_outputs(args.dump_outputs, {"placements": assign})
     R = max(args.rounds, 1)
     row_b = ROW_B.get(args.workload, 48)
     alg = (replaced / R) * wl.N * row_b + (replaced / R) * TASK_B
@@ -404,7 +432,7 @@ def run_churn(args, ranks, wl, eng, descs, ranges):
         # (a sharded round costs a propose + a commit launch per device plus the exchange, against the same two launches on one
         # engine: below the node count one engine's LDS holds, sharding cannot be faster)
         res["expected_speedup"] = "<1 below ~650k nodes: the node-range split exists for node sets one engine cannot hold"
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline(wl, budget_s=8.0)
     if rank == 0:
         emit_line(json.dumps(res))
@@ -432,7 +460,13 @@ def main():
     ap.add_argument("--shards", type=int, default=0, help="N=1 only: run the node-shard protocol over this many engines on the one GPU")
     ap.add_argument("--strict", action="store_true", help="--gpus N > 1: exit non-zero instead of falling back to the host-merged exchange when RCCL inside libswp.so is unusable")
     ap.add_argument("--host-merge", action="store_true", help="--shards: the round-2 protocol (proposals merged on the host) instead of the rounds on the device")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the end-to-end runs outside the timed region and the CPU oracle baseline "
+                         "(off by default: a plain run sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if world_env != args.gpus and world_env == 1 and args.gpus > 1:
@@ -470,6 +504,13 @@ def main():
                 placed = sum(1 for d in dec if d["NodeID"])
             st = s.e.stats()
         t_step = sum(ticks) / max(len(ticks), 1)
+        if args.dump_outputs:   # the last tick's decisions: the node of every task ("task<j>" on "n<i>"; -1: none), its state
+            import numpy as np
+            node, state = np.full(n_tasks, -1.0), np.zeros(n_tasks)
+            for d in dec:
+                j = int(d["ID"][len("task"):])
+                node[j], state[j] = int(d["NodeID"][1:]) if d["NodeID"] else -1, d["State"]
+            dump_outputs(args.dump_outputs, {"placements": node, "state": state})
         emit_line(json.dumps({"metric": f"task placements/sec, the reference's benchScheduler shape ({n_tasks // 1000}k tasks of one service x {n_nodes} nodes), end to end through Scheduler.tick()",
                           "value": n_tasks / t_step, "unit": "placements/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": t_step * 1e3,
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
@@ -550,12 +591,14 @@ def main():
         for _ in range(args.steps):
             rej = eng.enforce(nrec, trec)
         t_step = (time.perf_counter() - t0) / max(args.steps, 1)
+        if args.dump_outputs:   # (one flag per task record, in the order of the records: by node, then task id)
+            dump_outputs(args.dump_outputs, {"rejected": rej})
         res = {"metric": "constraint-enforcer sweep: (task, node) compliance checks/sec, end to end through swp_enforce",
                "value": len(order) / t_step, "unit": "task checks/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": t_step * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
                "data": "synthetic", "config": dict(wl.describe(), mode="enforce", tasks_checked=int(len(order)), nodes_swept=int(wl.N)),
                "rejected": int(rej.sum())}
-        if not args.no_cpu_baseline:
+        if args.cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import orc
             sample = min(wl.N, 400)
@@ -611,6 +654,8 @@ def main():
             out, _h = one_tick()
         torch.cuda.synchronize(); ranks.barrier()
         t_step = ranks.max_over_ranks(time.perf_counter() - t0) / max(args.steps, 1)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(placements=out, **({"explain": _h} if _h is not None else {})))
         if rank == 0:
             row_b = ROW_B.get(args.workload, 48)
             alg = wl.S * wl.N * row_b + wl.T * TASK_B          # pairs = S x N in grouped mode
@@ -627,7 +672,7 @@ def main():
                                 "note": "one launch = the whole tick (k_g2_static: a wave per static class over the chip, then k_groups2: S groups, one workgroup: a machine wave + 15 helper waves); end-to-end step time (no separate kernel events on this path). "
                                         "The tick is bound by the machine wave's instruction issue while it replays container/heap in the reference's exact order (candidates from the group's static class list, 64 to a chunk; a full heap admits the candidates with its second key by counting them and scatters them by post-order rank, "
                                         "a push that moves is sifted up by the wave, two-key heaps are sorted by the wave; parallel appends / rotation / fill where the keys allow), not by bytes: the fraction says how far from a streaming scan that is"}}
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.cpu_baseline:
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 import orc
                 o = orc.Oracle()
@@ -689,48 +734,56 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = ranks.max_over_ranks(elapsed)
     launches1 = eng.stats()["resolve_launches"]   # (before the end-to-end runs below add theirs)
-
-    # end to end, outside the timed region: what a caller of swp_schedule_batch waits for — de-duplication of the predicate
-    # sets + H2D of the descriptors (swp_batch_prepare), the device pass, D2H of placements AND explanation histograms
-    e2e, prep = [], []
-    for _ in range(3):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"placements": out})
+    end_to_end = None
+    if args.full:
+        # end to end, outside the timed region: what a caller of swp_schedule_batch waits for — de-duplication of the predicate
+        # sets + H2D of the descriptors (swp_batch_prepare), the device pass, D2H of placements AND explanation histograms
+        e2e, prep = [], []
+        for _ in range(3):
+            eng.state_restore()
+            t0 = time.perf_counter()
+            b2 = eng.batch_prepare(descs)
+            prep.append(time.perf_counter() - t0)
+            b2.run()
+            b2.results(want_hist=True)
+            e2e.append(time.perf_counter() - t0)
+            b2.free()
+        t_e2e = min(e2e)
+        t_prepare_warm = min(prep)   # (the first prepare of the process also pays for the device allocations: reported as "cold")
+        # the same for a caller that knows which tasks share a descriptor (the tasks of one service spec: swp_batch_prepare_templates)
+        import numpy as np
+        tmpl, tmpl_of_task = np.unique(descs, return_inverse=True)
+        e2e_t, prep_t = [], []
+        for _ in range(3):
+            eng.state_restore()
+            t0 = time.perf_counter()
+            b2 = eng.batch_prepare_templates(tmpl, tmpl_of_task)
+            prep_t.append(time.perf_counter() - t0)
+            b2.run()
+            out_t, _h = b2.results(want_hist=True)
+            e2e_t.append(time.perf_counter() - t0)
+            b2.free()
+        assert (out_t == out).all(), "swp_batch_prepare_templates: placements differ from swp_batch_prepare's"
+        # ... and what swp_schedule_batch costs in all: swp_batch_fetch also books the placements in the engine's host-side node mirror
+        # (per-node residuals and service counts, the service -> nodes index the next batch's exception lists are read off)
+        e2e_f = []
+        for _ in range(3):
+            eng.state_restore()
+            t0 = time.perf_counter()
+            b2 = eng.batch_prepare(descs)
+            b2.run()
+            out_f, _h = b2.fetch(want_hist=True)
+            e2e_f.append(time.perf_counter() - t0)
+            b2.free()
+        assert (out_f == out).all(), "swp_batch_fetch: placements differ from swp_batch_results'"
         eng.state_restore()
-        t0 = time.perf_counter()
-        b2 = eng.batch_prepare(descs)
-        prep.append(time.perf_counter() - t0)
-        b2.run()
-        b2.results(want_hist=True)
-        e2e.append(time.perf_counter() - t0)
-        b2.free()
-    t_e2e = min(e2e)
-    t_prepare_warm = min(prep)   # (the first prepare of the process also pays for the device allocations: reported as "cold")
-    # the same for a caller that knows which tasks share a descriptor (the tasks of one service spec: swp_batch_prepare_templates)
-    import numpy as np
-    tmpl, tmpl_of_task = np.unique(descs, return_inverse=True)
-    e2e_t, prep_t = [], []
-    for _ in range(3):
-        eng.state_restore()
-        t0 = time.perf_counter()
-        b2 = eng.batch_prepare_templates(tmpl, tmpl_of_task)
-        prep_t.append(time.perf_counter() - t0)
-        b2.run()
-        out_t, _h = b2.results(want_hist=True)
-        e2e_t.append(time.perf_counter() - t0)
-        b2.free()
-    assert (out_t == out).all(), "swp_batch_prepare_templates: placements differ from swp_batch_prepare's"
-    # ... and what swp_schedule_batch costs in all: swp_batch_fetch also books the placements in the engine's host-side node mirror
-    # (per-node residuals and service counts, the service -> nodes index the next batch's exception lists are read off)
-    e2e_f = []
-    for _ in range(3):
-        eng.state_restore()
-        t0 = time.perf_counter()
-        b2 = eng.batch_prepare(descs)
-        b2.run()
-        out_f, _h = b2.fetch(want_hist=True)
-        e2e_f.append(time.perf_counter() - t0)
-        b2.free()
-    assert (out_f == out).all(), "swp_batch_fetch: placements differ from swp_batch_results'"
-    eng.state_restore()
+        end_to_end = {"ms": t_e2e * 1e3, "placements_per_s": wl.T / t_e2e, "with_mirror_fold_ms": min(e2e_f) * 1e3,
+                      "includes": "swp_batch_prepare (predicate de-duplication + H2D of the task descriptors) + device pass + D2H of placements and Explain histograms",
+                      "swp_batch_prepare_ms": t_prepare_warm * 1e3, "swp_batch_prepare_cold_ms": t_prepare * 1e3,
+                      "with_templates": {"ms": min(e2e_t) * 1e3, "swp_batch_prepare_templates_ms": min(prep_t) * 1e3, "templates": int(len(tmpl)),
+                                         "note": "the caller names the template (service spec) of every task: no per-task de-duplication pass"}}
 
     st = eng.stats()
     K = max(args.steps, 1)
@@ -813,15 +866,12 @@ def main():
                      "clock_GHz": SHADER_GHZ, "measured_HBM_GBs": measured_gbs,
                      "note": "cycles of the matching wave's CU per task of the batch, at the peak engine clock; measured_HBM_GBs = PMC bytes per launch (roofline.traffic) / launch time"},
         "whole_job_algorithmic_GBs": alg_bytes_step / t_step / 1e9,
-        "end_to_end": {"ms": t_e2e * 1e3, "placements_per_s": wl.T / t_e2e, "with_mirror_fold_ms": min(e2e_f) * 1e3,
-                       "includes": "swp_batch_prepare (predicate de-duplication + H2D of the task descriptors) + device pass + D2H of placements and Explain histograms",
-                       "swp_batch_prepare_ms": t_prepare_warm * 1e3, "swp_batch_prepare_cold_ms": t_prepare * 1e3,
-                       "with_templates": {"ms": min(e2e_t) * 1e3, "swp_batch_prepare_templates_ms": min(prep_t) * 1e3, "templates": int(len(tmpl)),
-                                          "note": "the caller names the template (service spec) of every task: no per-task de-duplication pass"}},
         "host_prep_s": {"intern+descriptors": t_host_prep, "swp_batch_prepare": t_prepare},
         "resolver_raw": {k: st[k] for k in ("generic_tasks", "resolver_spins", "slow_path_tasks", "rebase_events", "batches")},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N=1 only (bounded sample, ~15 s of one host core)
+    if end_to_end is not None:
+        result["end_to_end"] = end_to_end
+    if rank == 0 and world == 1 and args.cpu_baseline:   # reported at N=1 only (bounded sample, ~15 s of one host core)
         result["cpu_baseline"] = cpu_baseline(wl)
     if rank == 0:
         emit_line(json.dumps(result))

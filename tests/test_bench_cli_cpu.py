@@ -60,3 +60,25 @@ def test_no_device_no_result_line(args):
     assert r.returncode != 0
     assert "no HIP device" in r.stderr
     assert result_lines(r.stdout) == []
+
+
+def test_dump_outputs_float64_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays; beyond the budget a fixed, seeded sample of rows (the same rows on every run) with its row numbers."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(-1, 99, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"placements": small})
+    got = np.load(tmp_path / "a" / "placements.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_B", 4096)
+    big = np.arange(10000, dtype=np.int64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"placements": big, "explain": np.ones((10000, 8), dtype=np.uint32)})
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["explain.npy", "explain_rows.npy", "placements.npy", "placements_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in files) <= 4096
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    rows = np.load(tmp_path / "b" / "placements_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "placements.npy"), big[rows].astype(np.float64))

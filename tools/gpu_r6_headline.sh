@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 timeout 1500 python -m pytest tests/test_engine_fullsize.py tests/test_engine_parity.py tests/test_engine_resolvers.py tests/test_engine_blocks.py tests/test_engine_shards.py tests/test_engine_dense.py tests/test_engine_generic.py -x -q > "$OUT/tests.log" 2>&1
 grep -n "passed\|failed\|error" "$OUT/tests.log" | tail -3
-b() { local name=$1; shift; timeout 300 python bench.py --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; python -c "
+b() { local name=$1; shift; timeout 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; python -c "
 import json
 try:
     d=json.load(open('$OUT/$name.json')); print('$name: ms_per_step %.3f value %.0f e2e %s' % (d['ms_per_step'], d['value'], d.get('end_to_end', {}).get('ms')))

@@ -33,8 +33,8 @@ trace shards4 --steps 2 --warmup 1 --workload cfg4 --tasks 200000 --nodes 40000 
 cd "$ROOT"
 python "$ROOT/tools/summarize_prof.py" "$OUT" "$TAG" "$SWP_COMMIT"
 cp "$OUT/${TAG}_pmc_summary.json" "$ROOT/profiles/" 2>/dev/null   # (this run's bench lines below read it)
-bj() { local name=$1; shift; timeout 600 python bench.py --steps 3 --warmup 1 "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/bench_$name.err"; }
-timeout 400 python bench.py > "$OUT/${TAG}_bench_cfg3.json" 2> "$OUT/bench_cfg3.err"
+bj() { local name=$1; shift; timeout 600 python bench.py --full --steps 3 --warmup 1 "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/bench_$name.err"; }
+timeout 400 python bench.py --full > "$OUT/${TAG}_bench_cfg3.json" 2> "$OUT/bench_cfg3.err"
 bj grouped --mode grouped
 bj churn --mode churn
 bj dense --tasks 100000 --nodes 1000 --services 10

@@ -41,8 +41,8 @@ python "$ROOT/tools/summarize_prof.py" "$OUT" "$TAG" "$SWP_COMMIT"
 cp "$OUT/${TAG}_pmc_summary.json" "$ROOT/profiles/" 2>/dev/null   # (this run's bench lines below read it)
 find "$OUT" -name "*kernel_trace.csv" -delete; find "$OUT" -name "*counter_collection.csv" -delete; find "$OUT" -name "*.db" -delete; find "$OUT" -name "*agent_info.csv" -delete
 rm -rf "$OUT"/pmc_fetch_*/ "$OUT"/pmc_write_*/ 2>/dev/null
-bj() { local name=$1; shift; timeout 600 python bench.py --steps 3 --warmup 1 "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/bench_$name.err"; }
-timeout 400 python bench.py > "$OUT/${TAG}_bench_cfg3.json" 2> "$OUT/bench_cfg3.err"
+bj() { local name=$1; shift; timeout 600 python bench.py --full --steps 3 --warmup 1 "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/bench_$name.err"; }
+timeout 400 python bench.py --full > "$OUT/${TAG}_bench_cfg3.json" 2> "$OUT/bench_cfg3.err"
 bj grouped --mode grouped
 bj churn --mode churn
 bj churn_shards4 --mode churn --shards 4 --no-cpu-baseline
