@@ -278,6 +278,7 @@ typedef struct { uint32_t kind; uint32_t key; } swp_spread;
 int swp_spread_set(swp_engine*, const swp_spread* levels, uint32_t n, uint32_t* id_out);
 
 #define SWP_TASK_RES_ENABLED 0x1u   /* ResourceFilter.SetTask returned true (filter.go:61-74) */
+#define SWP_TASK_UNCOUNTED 0x2u     /* DesiredState > COMPLETED: a placement does not count toward ActiveTasksCount* (nodeinfo.go:148) */
 #define SWP_TASK_MOUNTS_SHIFT 8     /* flags >> 8 = the task's mount set (swp_mount_set), 0 = no MountTypeCluster mounts */
 #define SWP_TASK_MOUNTS(set) ((uint32_t)(set) << SWP_TASK_MOUNTS_SHIFT)
 
@@ -487,6 +488,18 @@ int swp_commit(swp_engine*, const swp_placement* p, uint32_t n, int add_or_remov
 /* Pipeline.Process on ONE (task, node) pair == taskFitNode's check (scheduler.go:646-654).
  * *first_fail = -1 on pass, else the index of the first failing filter. */
 int swp_check_node(swp_engine*, const swp_task_desc* task, uint32_t node, int32_t* first_fail);
+
+/* taskFitNode for MANY preassigned tasks (processPreassignedTasks, scheduler.go:398-426, 646-690) in one device pass. Pair i is
+ * task templates[pairs[i].tmpl] on node pairs[i].node. Pairs on different nodes are independent; the pairs of one node are judged in
+ * array order, and a passing pair enters the nodeSet mirror — as a placement of swp_schedule_batch would: cpu / mem, task count,
+ * ActiveTasksCountByService (unless SWP_TASK_UNCOUNTED), host ports, generic counts less the request — before the next pair of that
+ * node is judged. first_fail[i] = -1 on pass, else the first failing filter 0..6 (as swp_check_node). Classes come from one pass
+ * over the templates. Everything is validated first and the call is all or nothing: on any error nothing was applied. Refused
+ * (SWP_EUNSUPPORTED): templates with cluster mounts (SWP_TASK_MOUNTS) — volume state is cluster-wide, such a task keeps swp_check_node
+ * + swp_choose_volumes — and templates with spread preferences, which swp_check_node refuses too. */
+typedef struct { uint32_t node; uint32_t tmpl; } swp_fit_pair;   /* 8 bytes */
+int swp_fit_pairs(swp_engine*, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs,
+                  int32_t* first_fail);
 
 /* constraintenforcer.rejectNoncompliantTasks (manager/orchestrator/constraintenforcer/constraint_enforcer.go:65-196)
  * over MANY nodes in one call: the enforcer's start-up sweep (Run, :45-52) or a burst of EventUpdateNode. Per node the

@@ -84,7 +84,10 @@ int swp_sched_delete_task(swp_sched*, const char* task_json, size_t len, int* ti
  * *decisions_json = JSON array of {ID, ServiceID, NodeID, State, Message, Err, OldState[, AssignedGenericResources]} — what
  * applySchedulingDecisions (:490-643) would write to the store. */
 int swp_sched_tick(swp_sched*, const char** decisions_json);
-/* processPreassignedTasks + taskFitNode (scheduler.go:398-426, 646-690) through swp_check_node */
+/* processPreassignedTasks + taskFitNode (scheduler.go:398-426, 646-690): the pending tasks in order, runs of them judged in one
+ * swp_fit_pairs call each (the per-node chain of the reference kept); tasks with cluster mounts or spread preferences, tasks already in
+ * their node's Tasks and tasks that reserve a generic kind their node lists irregularly go through swp_check_node one by one, as every
+ * task does when the engine does not export swp_fit_pairs */
 int swp_sched_process_preassigned(swp_sched*, const char** decisions_json);
 /* The failed half of applySchedulingDecisions (scheduler.go:472-487 after tick, :416-425 after processPreassignedTasks):
  * the caller could not commit a decision to the store (stale Meta.Version :533-545, node no longer READY :560-567, a

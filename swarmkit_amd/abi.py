@@ -80,6 +80,7 @@ class Stats(C.Structure):
 TASK_DTYPE = np.dtype([("service", "<u4"), ("flags", "<u4"), ("cpu", "<i8"), ("mem", "<i8"), ("constraint_set", "<u4"),
                        ("platform_set", "<u4"), ("plugin_set", "<u4"), ("port_set", "<u4"), ("max_replicas", "<u8"),
                        ("spec_version", "<u8"), ("spread_set", "<u4"), ("generic_set", "<u4")])
+FIT_PAIR_DTYPE = np.dtype([("node", "<u4"), ("tmpl", "<u4")])   # swp_fit_pair
 PLACEMENT_DTYPE = np.dtype([("node", "<u4"), ("service", "<u4"), ("cpu", "<i8"), ("mem", "<i8"), ("port_set", "<u4"), ("counted", "<u4")])
 ENF_NODE_DTYPE = np.dtype([("node", "<u4"), ("first_task", "<u4"), ("n_tasks", "<u4"), ("reserved", "<u4"), ("cpu", "<i8"), ("mem", "<i8")])
 ENF_TASK_DTYPE = np.dtype([("cpu", "<i8"), ("mem", "<i8"), ("constraint_set", "<u4"), ("flags", "<u4"), ("desired_state", "<u4"), ("state", "<u4")])
@@ -108,7 +109,7 @@ EXPORTS = [
     "swp_create", "swp_destroy", "swp_reset", "swp_intern", "swp_intern_lookup", "swp_node_upsert", "swp_node_update_dynamic",
     "swp_node_remove", "swp_node_get", "swp_node_set_svc_count", "swp_node_get_svc_count", "swp_node_set_failures", "swp_node_port",
     "swp_constraint_set", "swp_platform_set", "swp_plugin_set", "swp_port_set", "swp_spread_set", "swp_schedule_groups", "swp_schedule_batch", "swp_batch_prepare",
-    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_enforce", "swp_node_matches",
+    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_enforce", "swp_node_matches",
     "swp_stats", "swp_strerror", "swp_last_error", "swp_abi_check", "swp_node_update_dynamic_many", "swp_node_get_many", "swp_shardset_create",
     "swp_shard_begin", "swp_shard_propose", "swp_shard_merge", "swp_shard_commit", "swp_shard_end", "swp_shard_run", "swp_rccl_available", "swp_rccl_unique_id", "swp_rccl_init", "swp_rccl_finalize", "swp_shard_run_rank", "swp_shard_verdict",
     # include/swp_sched.h — the host layer above the engine
@@ -117,6 +118,8 @@ EXPORTS = [
     "swp_sched_delete_task", "swp_sched_tick", "swp_sched_process_preassigned", "swp_sched_reject_decision", "swp_sched_commit_plan", "swp_sched_reject_decisions", "swp_sched_reject_node", "swp_sched_task_desc", "swp_sched_constraint_set", "swp_sched_enforce", "swp_sched_update_volume", "swp_sched_volume_info", "swp_sched_free_volumes",
     "swp_constraint_parse", "swp_key_equal_fold", "swp_explain", "swp_parse_ip",
 ]
+# exports a library built against this header may lack (the host layer's CPU test double): the host layer declares them weak
+OPTIONAL = {"swp_fit_pairs"}
 
 
 class Unsupported(NotImplementedError):
@@ -208,6 +211,7 @@ def load_library(path=None):
         "swp_rccl_finalize": ([vp], C.c_int),
         "swp_shard_run_rank": ([vp, vp, vp, u32, vp, vp], C.c_int),
         "swp_check_node": ([vp, P(TaskDesc), u32, P(i32)], C.c_int),
+        "swp_fit_pairs": ([vp, vp, u32, vp, u32, vp], C.c_int),
         "swp_enforce": ([vp, vp, u32, vp, u32, vp], C.c_int),
         "swp_node_matches": ([vp, vp, u32, vp, u32], C.c_int),
         "swp_stats": ([vp, P(Stats)], C.c_int),
@@ -247,6 +251,8 @@ def load_library(path=None):
         "swp_parse_ip": ([cp, sz, P(C.c_uint8), P(C.c_int)], C.c_int),
     })
     for name, (args, res) in sig.items():
+        if name in OPTIONAL and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res
@@ -591,6 +597,17 @@ class Engine:
         ff = C.c_int32()
         self._ck(self.L.swp_check_node(self.h, C.cast(t.ctypes.data, C.POINTER(TaskDesc)), node, C.byref(ff)))
         return ff.value
+
+    def fit_pairs(self, templates, pairs):
+        """swp_fit_pairs: taskFitNode for many (node, template) pairs, judged per node in array order with the earlier passing pairs
+        applied. pairs: FIT_PAIR_DTYPE or (node, tmpl) tuples. Returns first_fail per pair (int32; -1 = passed and applied)."""
+        templates = np.ascontiguousarray(templates, dtype=TASK_DTYPE)
+        if not isinstance(pairs, np.ndarray) or pairs.dtype != FIT_PAIR_DTYPE:
+            pairs = np.array([tuple(p) for p in pairs], dtype=FIT_PAIR_DTYPE)
+        pairs = np.ascontiguousarray(pairs)
+        ff = np.empty(len(pairs), dtype=np.int32)
+        self._ck(self.L.swp_fit_pairs(self.h, templates.ctypes.data, len(templates), pairs.ctypes.data, len(pairs), ff.ctypes.data))
+        return ff
 
     def stats(self):
         s = Stats()

@@ -857,4 +857,92 @@ __global__ void k_check_pair(CheckArgs a) {
     *a.out = ff;
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_fit_pairs — taskFitNode for many preassigned tasks (processPreassignedTasks, scheduler.go:398-426, 646-690).
+// The pairs come grouped by node (segments, pair order kept inside each); one thread walks one segment in order and judges every
+// pair with k_check_pair's chain against the node as the earlier passing pairs of the segment left it (NodeInfo.addTask between
+// two tasks): cpu / mem in registers, the generic counts, host-port claims and per-service counts in slots of its own. Different
+// nodes are independent. The thread is the only writer of its node, its slots and its pairs' verdicts: plain loads and stores.
+// ---------------------------------------------------------------------------------------------
+struct FitTmpl {
+    RTask rt;                 // the template's record (build_batch): classes, reservations, flags, MaxReplicas
+    u32 gen_off, n_gen;       // its generic reservations: gkind / gval[gen_off .. +n_gen)
+    u32 n_ports, pad;         // ports in its port set: a pair's port slots are port_slot[pair.port_off .. +n_ports)
+};
+static_assert(sizeof(FitTmpl) == 80, "FitTmpl layout");
+struct FitPair { u32 idx, tmpl, svc_slot, port_off; };   // idx: the pair's position in the caller's array
+struct FitArgs {
+    u32 n_seg, n_words, gstride, pad;
+    const u32* seg_node;      // [n_seg]
+    const u32* seg_off;       // [n_seg + 1] into pairs
+    const FitPair* pairs;
+    const FitTmpl* tm;
+    const u32* gkind;
+    const int32_t* gval;
+    const u32* port_slot;
+    u32* port_taken;          // per (segment, port): 1 = held on the node (its initial value: HostNode.ports)
+    u32* svc_cnt;             // per (segment, service): ActiveTasksCountByService (initial value: HostNode.svc)
+    const u64* ready;
+    const u64* con;
+    const u64* plat;
+    const u64* plug;
+    i64* cpu;
+    i64* mem;
+    u32* total;
+    int32_t* gcnt;            // [kind][gstride]
+    int32_t* out;             // first failing filter per pair, caller's order; -1 = passed (and applied)
+};
+__global__ __launch_bounds__(256) void k_fit_pairs(FitArgs a) {
+    const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.n_seg) return;
+    // (the host passes present nodes only: DEV_VALID is set for every one of them, k_check_pair's -2 cannot happen here)
+    const u32 n = a.seg_node[s], w = n >> 6;
+    const u64 bit = 1ull << (n & 63);
+    const bool ready = (a.ready[w] & bit) != 0;
+    i64 cpu = a.cpu[n], mem = a.mem[n];
+    u32 total = a.total[n];
+    const u32 p1 = a.seg_off[s + 1];
+    for (u32 p = a.seg_off[s]; p < p1; ++p) {
+        const FitPair q = a.pairs[p];
+        const FitTmpl& t = a.tm[q.tmpl];
+        const u32 fl = t.rt.flags;
+        int ff = -1;
+        if (!ready) ff = 0;
+        else if ((fl & RT_RES) && !(t.rt.cpu <= cpu && t.rt.mem <= mem)) ff = 1;
+        else if ((fl & RT_RES) && [&] {
+                     for (u32 g = 0; g < t.n_gen; ++g)
+                         if (a.gcnt[(size_t)a.gkind[t.gen_off + g] * a.gstride + n] < a.gval[t.gen_off + g]) return true;   // HasEnough, validate.go:24-52
+                     return false;
+                 }())
+            ff = 1;
+        else if (t.rt.cls_plug && !(a.plug[(size_t)t.rt.cls_plug * a.n_words + w] & bit)) ff = 2;
+        else if (t.rt.cls_con && !(a.con[(size_t)t.rt.cls_con * a.n_words + w] & bit)) ff = 3;
+        else if (t.rt.cls_plat && !(a.plat[(size_t)t.rt.cls_plat * a.n_words + w] & bit)) ff = 4;
+        else if ((fl & RT_PORTS) && [&] {
+                     for (u32 k = 0; k < t.n_ports; ++k)
+                         if (a.port_taken[a.port_slot[q.port_off + k]]) return true;   // HostPortFilter, filter.go:335-350
+                     return false;
+                 }())
+            ff = 5;
+        else if ((fl & RT_MAXREP) && !((u64)a.svc_cnt[q.svc_slot] < t.rt.maxrep)) ff = 6;
+        a.out[q.idx] = ff;
+        if (ff != -1) continue;
+        // NodeInfo.addTask (nodeinfo.go:128-154): what a placement of swp_schedule_batch books
+        cpu -= t.rt.cpu;
+        mem -= t.rt.mem;
+        for (u32 g = 0; g < t.n_gen; ++g) {
+            int32_t* c = a.gcnt + (size_t)a.gkind[t.gen_off + g] * a.gstride + n;
+            *c = max(*c - a.gval[t.gen_off + g], 0);   // (an entry that reaches 0 leaves the list)
+        }
+        if (!(fl & RT_UNCOUNTED)) {
+            ++total;
+            ++a.svc_cnt[q.svc_slot];
+        }
+        for (u32 k = 0; k < t.n_ports; ++k) a.port_taken[a.port_slot[q.port_off + k]] = 1u;
+    }
+    a.cpu[n] = cpu;
+    a.mem[n] = mem;
+    a.total[n] = total;
+}
+
 }  // namespace swpdev

@@ -543,6 +543,7 @@ struct swp_engine {
     DevBuf d_save_cpu, d_save_mem, d_save_total;
     DevBuf d_gcnt, d_save_gcnt;      // [dev_gkinds][ncap] int32: generic counts per (kind, node), part of the dynamic state
     uint32_t dev_gkinds = 0;
+    DevBuf d_fit;                    // swp_fit_pairs' arena: its tables, slots and verdicts (one upload)
     bool dev_static_dirty = true;    // flags/os/arch/attr/ip/plugins need a re-upload
     bool dev_dynamic_dirty = true;   // cpu/mem/total need a re-upload
     // Rows that swp_node_update_dynamic changed since the last flush (a drain flips one flag word, a correction moves one node's
@@ -2438,6 +2439,7 @@ int state_save(swp_engine*);
 int state_restore(swp_engine*);
 int commit(swp_engine*, const swp_placement*, uint32_t, int);
 int check_node(swp_engine*, const swp_task_desc*, uint32_t, int32_t*);
+int fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*);
 int enforce(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, uint8_t*);
 int node_matches(swp_engine*, const uint32_t*, uint32_t, uint64_t*, uint32_t);
 int stats(swp_engine*, swp_stats_t*);
@@ -4391,6 +4393,174 @@ int swp_check_node(swp_engine* e, const swp_task_desc* task, uint32_t node, int3
         (void)att;
         (void)na;
         if (!h[SWP_MAX_MOUNTS + 2]) *first_fail = 7;
+    }
+    return SWP_OK;
+}
+
+int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail) {
+    if (e && e->set) return ss::fit_pairs(e, templates, n_templates, pairs, n_pairs, first_fail);
+    if (!e || (!templates && n_templates) || (!pairs && n_pairs) || (!first_fail && n_pairs)) return SWP_EINVAL;
+    if (n_pairs == 0) return SWP_OK;
+    // everything is checked before the device is touched: a refused call leaves the mirror as it was
+    for (uint32_t t = 0; t < n_templates; ++t) {
+        const swp_task_desc& d = templates[t];
+        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+        if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
+        if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
+        if (d.service >= e->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
+        if (d.constraint_set >= e->con_sets.size() || d.platform_set >= e->plat_sets.size() || d.plugin_set >= e->plug_sets.size() ||
+            d.port_set >= e->port_sets.size() || d.generic_set >= e->gen_sets.size())
+            return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown predicate set", t);
+    }
+    const uint32_t NN = (uint32_t)e->nodes.size();
+    for (uint32_t i = 0; i < n_pairs; ++i) {
+        if (pairs[i].tmpl >= n_templates) return e->fail(SWP_EINVAL, "fit_pairs: pair %u names template %u of %u", i, pairs[i].tmpl, n_templates);
+        if (pairs[i].node >= NN || !e->nodes[pairs[i].node].present) return e->fail(SWP_ENOTFOUND, "fit_pairs: pair %u: node %u is not in the nodeSet mirror", i, pairs[i].node);
+    }
+    (void)hipSetDevice(e->device);
+    // classes: one pass over the templates (the spec version selects a failure bucket only: not read here, and one call may carry
+    // two revisions of a service)
+    HostSpan sp("fit_pairs: classes");
+    std::vector<swp_task_desc> td(templates, templates + n_templates);
+    std::vector<uint32_t> ident(n_templates);
+    for (uint32_t t = 0; t < n_templates; ++t) {
+        td[t].spec_version = 0;
+        ident[t] = t;
+    }
+    swp_batch* b = nullptr;
+    int rc = swp_batch_prepare_templates(e, td.data(), n_templates, ident.data(), n_templates, &b);
+    if (rc) return rc;
+    std::unique_ptr<swp_batch, void (*)(swp_batch*)> guard(b, [](swp_batch* x) { delete x; });
+    if ((rc = run_classes(e, b))) return rc;
+    sp.next("fit_pairs: segments");
+    // the pairs by node, pair order kept inside a node (counting sort): one segment per node
+    std::vector<uint32_t> pos(NN + 1, 0), order(n_pairs);
+    for (uint32_t i = 0; i < n_pairs; ++i) pos[pairs[i].node + 1]++;
+    uint32_t n_seg = 0;
+    for (uint32_t n = 0; n < NN; ++n) {
+        n_seg += pos[n + 1] ? 1u : 0u;
+        pos[n + 1] += pos[n];
+    }
+    for (uint32_t i = 0; i < n_pairs; ++i) order[pos[pairs[i].node]++] = i;   // (pos[n] ends at the start of node n + 1)
+    std::vector<FitTmpl> ft(n_templates);
+    std::vector<uint32_t> gkind, ports_of_tmpl;
+    std::vector<int32_t> gval;
+    for (uint32_t t = 0; t < n_templates; ++t) {
+        FitTmpl& f = ft[t];
+        std::memset(&f, 0, sizeof f);
+        f.rt = b->rt[t];
+        f.gen_off = (uint32_t)gkind.size();
+        if (templates[t].generic_set)
+            for (const swp_generic& g : e->gen_sets[templates[t].generic_set]) {
+                gkind.push_back(g.kind);
+                gval.push_back((int32_t)g.value);
+            }
+        f.n_gen = (uint32_t)gkind.size() - f.gen_off;
+        f.n_ports = templates[t].port_set ? (uint32_t)e->port_sets[templates[t].port_set].size() : 0u;
+    }
+    // per segment: a slot per service (its count on the node) and per host port (held or not) the segment's pairs name
+    std::vector<uint32_t> seg_node(n_seg), seg_off(n_seg + 1), port_slot, port_taken, svc_cnt;
+    std::vector<FitPair> fp(n_pairs);
+    const size_t n_svc_ids = e->spaces[SWP_SPACE_SERVICE].strs.size();
+    std::vector<uint32_t> svc_stamp(n_svc_ids, 0xFFFFFFFFu), svc_slot(n_svc_ids, 0);
+    std::unordered_map<uint64_t, uint32_t> port_of_key;
+    for (uint32_t s = 0, p = 0; p < n_pairs; ++s) {
+        const uint32_t node = pairs[order[p]].node;
+        const HostNode& h = e->nodes[node];
+        seg_node[s] = node;
+        seg_off[s] = p;
+        port_of_key.clear();
+        for (; p < n_pairs && pairs[order[p]].node == node; ++p) {
+            const uint32_t i = order[p], t = pairs[i].tmpl;
+            const swp_task_desc& d = templates[t];
+            FitPair& q = fp[p];
+            q.idx = i;
+            q.tmpl = t;
+            if (svc_stamp[d.service] != s) {
+                svc_stamp[d.service] = s;
+                svc_slot[d.service] = (uint32_t)svc_cnt.size();
+                auto it = h.svc.find(d.service);
+                svc_cnt.push_back(it == h.svc.end() ? 0u : it->second);
+            }
+            q.svc_slot = svc_slot[d.service];
+            q.port_off = (uint32_t)port_slot.size();
+            if (d.port_set)
+                for (const swp_port& pt : e->port_sets[d.port_set]) {
+                    const uint64_t k = port_key(pt.protocol, pt.port);
+                    auto ins = port_of_key.emplace(k, (uint32_t)port_taken.size());
+                    if (ins.second) port_taken.push_back(h.ports.count(k) ? 1u : 0u);
+                    port_slot.push_back(ins.first->second);
+                }
+        }
+    }
+    seg_off[n_seg] = n_pairs;
+    if (port_taken.empty()) port_taken.push_back(0);   // (no array is empty: every view below points at memory of its own)
+    if (port_slot.empty()) port_slot.push_back(0);
+    if (gkind.empty()) {
+        gkind.push_back(0);
+        gval.push_back(0);
+    }
+    // one arena, one upload: the tables, the slots, the verdicts at the end
+    sp.next("fit_pairs: upload + k_fit_pairs + wait");
+    size_t off = 0;
+    auto place = [&off](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_node = place(seg_node.size() * 4), o_soff = place(seg_off.size() * 4), o_pair = place(fp.size() * sizeof(FitPair)),
+                 o_tm = place(ft.size() * sizeof(FitTmpl)), o_gk = place(gkind.size() * 4), o_gv = place(gval.size() * 4),
+                 o_ps = place(port_slot.size() * 4), o_pt = place(port_taken.size() * 4), o_sc = place(svc_cnt.size() * 4), up = off,
+                 o_out = place((size_t)n_pairs * 4);
+    std::vector<unsigned char> blob(up);
+    auto put = [&blob](size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(blob.data() + at, src, bytes); };
+    put(o_node, seg_node.data(), seg_node.size() * 4);
+    put(o_soff, seg_off.data(), seg_off.size() * 4);
+    put(o_pair, fp.data(), fp.size() * sizeof(FitPair));
+    put(o_tm, ft.data(), ft.size() * sizeof(FitTmpl));
+    put(o_gk, gkind.data(), gkind.size() * 4);
+    put(o_gv, gval.data(), gval.size() * 4);
+    put(o_ps, port_slot.data(), port_slot.size() * 4);
+    put(o_pt, port_taken.data(), port_taken.size() * 4);
+    put(o_sc, svc_cnt.data(), svc_cnt.size() * 4);
+    HIPCHECK(e, e->d_fit.reserve(off));
+    unsigned char* base = static_cast<unsigned char*>(e->d_fit.p);
+    HIPCHECK(e, hipMemcpyAsync(base, blob.data(), up, hipMemcpyHostToDevice, e->stream));
+    FitArgs fa{};
+    fa.n_seg = n_seg;
+    fa.n_words = n_words_of(e->n_nodes);
+    fa.gstride = e->ncap;
+    fa.seg_node = reinterpret_cast<const u32*>(base + o_node);
+    fa.seg_off = reinterpret_cast<const u32*>(base + o_soff);
+    fa.pairs = reinterpret_cast<const FitPair*>(base + o_pair);
+    fa.tm = reinterpret_cast<const FitTmpl*>(base + o_tm);
+    fa.gkind = reinterpret_cast<const u32*>(base + o_gk);
+    fa.gval = reinterpret_cast<const int32_t*>(base + o_gv);
+    fa.port_slot = reinterpret_cast<const u32*>(base + o_ps);
+    fa.port_taken = reinterpret_cast<u32*>(base + o_pt);
+    fa.svc_cnt = reinterpret_cast<u32*>(base + o_sc);
+    fa.ready = e->d_ready.as<u64>();
+    fa.con = b->d_con.as<u64>();
+    fa.plat = b->d_plat.as<u64>();
+    fa.plug = b->d_plug.as<u64>();
+    fa.cpu = e->d_cpu.as<long long>();
+    fa.mem = e->d_mem.as<long long>();
+    fa.total = e->d_total.as<uint32_t>();
+    fa.gcnt = e->d_gcnt.as<int32_t>();
+    fa.out = reinterpret_cast<int32_t*>(base + o_out);
+    hipLaunchKernelGGL(k_fit_pairs, dim3((n_seg + 255) / 256), dim3(256), 0, e->stream, fa);
+    HIPCHECK(e, hipGetLastError());
+    HIPCHECK(e, hipMemcpyAsync(first_fail, base + o_out, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    // the passing pairs into the host mirror, as swp_batch_fetch folds a batch's placements (the device holds them already)
+    sp.next("fit_pairs: placements into the node mirror");
+    {
+        std::vector<BulkItem> bulk;
+        bulk.reserve(n_pairs);
+        for (uint32_t i = 0; i < n_pairs; ++i) {
+            if (first_fail[i] != -1) continue;
+            const swp_task_desc& d = templates[pairs[i].tmpl];
+            if (!d.port_set && !d.generic_set && !(d.flags & SWP_TASK_UNCOUNTED)) bulk.push_back(BulkItem{pairs[i].node, d.service, d.cpu, d.mem});
+            else host_apply_placement(e, pairs[i].node, d.service, d.cpu, d.mem, d.port_set, !(d.flags & SWP_TASK_UNCOUNTED), true, d.generic_set);
+        }
+        BulkScratch scr;
+        host_apply_bulk(e, bulk, true, scr);
     }
     return SWP_OK;
 }

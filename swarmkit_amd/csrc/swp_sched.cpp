@@ -35,6 +35,10 @@
 #include "swp_json.hpp"
 #include "swp_tables.hpp"
 
+// Weak: an engine that does not export swp_fit_pairs (the CPU test double of tests/fake_swp.cpp) leaves it null, and
+// processPreassignedTasks then judges every task with swp_check_node, one call per task.
+extern "C" int swp_fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*) __attribute__((weak));
+
 namespace swp {
 
 using json::Value;
@@ -1040,59 +1044,179 @@ class Scheduler {
     }
 
     // ---------------------------------------------------------------------------------------------- preassigned
-    // processPreassignedTasks + taskFitNode, scheduler.go:398-426, 646-690
+    // processPreassignedTasks + taskFitNode, scheduler.go:398-426, 646-690. The pending tasks are walked in order; runs of them are
+    // judged in ONE swp_fit_pairs call (the engine keeps the reference's per-node chain: a passing task is on its node before the next
+    // task of that node is judged). A task the call cannot stand for goes through the per-task path below, behind the run before it:
+    // cluster mounts (volume state is cluster-wide), spread preferences (swp_check_node refuses them), a task already in its node's
+    // Tasks (addTask's state-change branches) and a generic kind its node lists irregularly (the engine's count -= request is not
+    // the reference's arithmetic there). Without swp_fit_pairs (an engine that does not export it) every task takes the per-task path.
+    struct PreItem {
+        std::string tid;
+        Value t;
+        NodeInfo* ni;
+        uint32_t tmpl;   // into the run's templates; NO_TMPL: taskDesc threw, `why` is its Deferred line
+        std::string why;
+    };
     std::string processPreassignedTasks() {
         Decisions decisions;
         lastDecisions_.erase_if([](const PendingDecision& d) { return d.preassigned; });
+        std::vector<PreItem> run;
+        std::vector<swp_task_desc> tmpls;
+        std::unordered_map<std::string, uint32_t> tmplOf;
+        auto flush = [&] {
+            flushPreassigned(run, tmpls, decisions);
+            run.clear();
+            tmpls.clear();
+            tmplOf.clear();
+        };
         for (auto& kv : pendingPreassignedTasks_.snapshot()) {
             const std::string& tid = kv.first;
             const Value& t = kv.second;
             auto n = nodes_.find(as_str(t.get("NodeID")));
             if (n == nodes_.end()) continue;   // node not (yet) known: the task stays pending, :651-656
-            Value newT = t.shallow_copy();
-            int32_t ff = -1;
+            if (swp_fit_pairs == nullptr) {
+                preassignedOne(tid, t, n->second, decisions);
+                continue;
+            }
+            swp_task_desc d;
             try {
-                const swp_task_desc d = taskDesc(t);
-                ck(swp_check_node(e_, &d, n->second.idx, &ff), "swp_check_node");
-            } catch (const Fail& f) {   // the engine cannot judge this task: it stays pending, the loop carries on
-                last_error = f.msg;
-                const bool from_engine = !engine_detail_.empty() && f.msg.size() >= engine_detail_.size() &&
-                                         f.msg.compare(f.msg.size() - engine_detail_.size(), engine_detail_.size(), engine_detail_) == 0;
-                const std::string why = "swp: deferred to the host scheduler: " + (from_engine ? engine_detail_ : f.msg);
-                decisions.begin(t, t, &why);
+                d = taskDesc(t);
+            } catch (const Fail& f) {   // deferred in place (as the per-task path would defer it)
+                run.push_back(PreItem{tid, t, &n->second, NO_TMPL, deferredWhy(f)});
+                continue;
+            }
+            if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) || d.spread_set || !clusterMounts(t).empty() || n->second.Tasks.find(tid) != nullptr ||
+                reservesIrregular(t, n->second)) {
+                flush();
+                preassignedOne(tid, t, n->second, decisions, &d);
+                continue;
+            }
+            const std::string key(reinterpret_cast<const char*>(&d), sizeof d);
+            auto ins = tmplOf.emplace(key, (uint32_t)tmpls.size());
+            if (ins.second) tmpls.push_back(d);
+            run.push_back(PreItem{tid, t, &n->second, ins.first->second, std::string()});
+        }
+        flush();
+        return decisions.finish();
+    }
+    std::string deferredWhy(const Fail& f) {
+        last_error = f.msg;
+        const bool from_engine = !engine_detail_.empty() && f.msg.size() >= engine_detail_.size() &&
+                                 f.msg.compare(f.msg.size() - engine_detail_.size(), engine_detail_.size(), engine_detail_) == 0;
+        return "swp: deferred to the host scheduler: " + (from_engine ? engine_detail_ : f.msg);
+    }
+    // the task reserves a generic kind its node lists more than once (pushGeneric keeps irregularGeneric_)
+    bool reservesIrregular(const Value& t, const NodeInfo& ni) {
+        if (irregularGeneric_.empty()) return false;
+        auto irr = irregularGeneric_.find(as_str(ni.node.get("ID")));
+        if (irr == irregularGeneric_.end()) return false;
+        for (const generic::Res& r : generic::decode(at(&t, "Spec", "Resources", "Reservations", "Generic")))
+            if (irr->second.count(r.kind)) return true;
+        return false;
+    }
+    // one swp_fit_pairs call for a run, then the decisions in the run's order; the engine applied the passing tasks already, what is
+    // left is the host half of addTask (nodeinfo.go:128-137: Claim, Tasks). A refused call applied nothing: the run goes through the
+    // per-task path, which reproduces its Deferred lines.
+    void flushPreassigned(const std::vector<PreItem>& run, const std::vector<swp_task_desc>& tmpls, Decisions& decisions) {
+        if (run.empty()) return;
+        std::vector<swp_fit_pair> pairs;
+        pairs.reserve(run.size());
+        for (const PreItem& it : run)
+            if (it.tmpl != NO_TMPL) pairs.push_back(swp_fit_pair{it.ni->idx, it.tmpl});
+        std::vector<int32_t> ff(pairs.size(), -1);
+        if (!pairs.empty() && swp_fit_pairs(e_, tmpls.data(), (uint32_t)tmpls.size(), pairs.data(), (uint32_t)pairs.size(), ff.data()) != SWP_OK) {
+            for (const PreItem& it : run) preassignedOne(it.tid, it.t, *it.ni, decisions);
+            return;
+        }
+        std::vector<NodeInfo*> claimed;
+        size_t k = 0;
+        for (const PreItem& it : run) {
+            if (it.tmpl == NO_TMPL) {
+                decisions.begin(it.t, it.t, &it.why);
                 decisions.field("Deferred", Value::boolean(true));
                 decisions.end();
                 continue;
             }
-            if (ff >= 0) {
+            const int32_t f = ff[k++];
+            Value newT = it.t.shallow_copy();
+            if (f >= 0) {
                 uint32_t hist[SWP_NFILTERS] = {0};
-                hist[ff] = 1;
-                Value status = statusCopy(t);
+                hist[f] = 1;
+                Value status = statusCopy(it.t);
                 status.set("Err", Value::str(explain(hist)));   // newT.Status.Err = s.pipeline.Explain(), :660
                 newT.set("Status", status);
-                allTasks_[tid] = newT;
-            } else if (!chooseForPreassigned(t, n->second, newT)) {   // scheduler.go:663-674: the error string is the task's new status
-                allTasks_[tid] = newT;
+                allTasks_[it.tid] = newT;
             } else {
                 Value status = Value::object();
                 status.set("State", Value::integer(ASSIGNED));
                 status.set("Message", Value::str("scheduler confirmed task can run on preassigned node"));
                 newT.set("Status", status);
-                allTasks_[tid] = newT;
-                addTask(n->second, newT);
-                pendingPreassignedTasks_.erase(tid);
-                // taskFitNode hands addTask the task the decision carries (scheduler.go:676-688): what Claim assigned is part of decision.new
-                auto st = allTasks_.find(tid);
-                if (st != allTasks_.end() && st->second.get("AssignedGenericResources")) newT.set("AssignedGenericResources", *st->second.get("AssignedGenericResources"));
+                // addTask's host half (:128-137): a fresh AssignedGenericResources, Claim against the node's available list
+                NodeInfo& ni = *it.ni;
+                Value stored = newT.shallow_copy();
+                generic::List assigned;
+                const generic::List want = generic::decode(at(&it.t, "Spec", "Resources", "Reservations", "Generic"));
+                generic::claim(&ni.availGeneric, &assigned, want);
+                stored.set("AssignedGenericResources", generic::encode(assigned));
+                ni.Tasks.put(it.tid, stored);
+                allTasks_[it.tid] = stored;
+                pendingPreassignedTasks_.erase(it.tid);
+                newT.set("AssignedGenericResources", *stored.get("AssignedGenericResources"));
+                if (!want.empty() && (claimed.empty() || claimed.back() != &ni)) claimed.push_back(&ni);
             }
-            lastDecisions_[tid] = PendingDecision{t, true};
-            decisions.begin(t, newT);
+            lastDecisions_[it.tid] = PendingDecision{it.t, true};
+            decisions.begin(it.t, newT);
             const Value* ag = newT.get("AssignedGenericResources");
             if (ag && ag->is_arr() && ag->size() > 0) decisions.field("AssignedGenericResources", *ag);
             if (newT.get("Volumes") != nullptr && task_state(at(&newT, "Status", "State")) == ASSIGNED) decisions.field("Volumes", *newT.get("Volumes"));
             decisions.end();
         }
-        return decisions.finish();
+        // the counts the engine holds already; pushGeneric keeps irregularGeneric_ current
+        std::sort(claimed.begin(), claimed.end());
+        claimed.erase(std::unique(claimed.begin(), claimed.end()), claimed.end());
+        for (NodeInfo* ni : claimed) pushGeneric(*ni);
+    }
+    // one pending task the per-task way: swp_check_node, then addTask (swp_commit) on a pass
+    void preassignedOne(const std::string& tid, const Value& t, NodeInfo& ni, Decisions& decisions, const swp_task_desc* known = nullptr) {
+        Value newT = t.shallow_copy();
+        int32_t ff = -1;
+        try {
+            const swp_task_desc d = known ? *known : taskDesc(t);
+            ck(swp_check_node(e_, &d, ni.idx, &ff), "swp_check_node");
+        } catch (const Fail& f) {   // the engine cannot judge this task: it stays pending, the loop carries on
+            const std::string why = deferredWhy(f);
+            decisions.begin(t, t, &why);
+            decisions.field("Deferred", Value::boolean(true));
+            decisions.end();
+            return;
+        }
+        if (ff >= 0) {
+            uint32_t hist[SWP_NFILTERS] = {0};
+            hist[ff] = 1;
+            Value status = statusCopy(t);
+            status.set("Err", Value::str(explain(hist)));   // newT.Status.Err = s.pipeline.Explain(), :660
+            newT.set("Status", status);
+            allTasks_[tid] = newT;
+        } else if (!chooseForPreassigned(t, ni, newT)) {   // scheduler.go:663-674: the error string is the task's new status
+            allTasks_[tid] = newT;
+        } else {
+            Value status = Value::object();
+            status.set("State", Value::integer(ASSIGNED));
+            status.set("Message", Value::str("scheduler confirmed task can run on preassigned node"));
+            newT.set("Status", status);
+            allTasks_[tid] = newT;
+            addTask(ni, newT);
+            pendingPreassignedTasks_.erase(tid);
+            // taskFitNode hands addTask the task the decision carries (scheduler.go:676-688): what Claim assigned is part of decision.new
+            auto st = allTasks_.find(tid);
+            if (st != allTasks_.end() && st->second.get("AssignedGenericResources")) newT.set("AssignedGenericResources", *st->second.get("AssignedGenericResources"));
+        }
+        lastDecisions_[tid] = PendingDecision{t, true};
+        decisions.begin(t, newT);
+        const Value* ag = newT.get("AssignedGenericResources");
+        if (ag && ag->is_arr() && ag->size() > 0) decisions.field("AssignedGenericResources", *ag);
+        if (newT.get("Volumes") != nullptr && task_state(at(&newT, "Status", "State")) == ASSIGNED) decisions.field("Volumes", *newT.get("Volumes"));
+        decisions.end();
     }
 
     // chooseTaskVolumes for a preassigned task on its node (scheduler.go:663-677): the attachments go into newT — nothing is reserved,

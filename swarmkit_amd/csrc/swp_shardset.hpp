@@ -602,6 +602,45 @@ int check_node(swp_engine* e, const swp_task_desc* task, uint32_t node, int32_t*
     return take_error(e, S.sh[g], swp_check_node(S.sh[g], task, l, first_fail));
 }
 
+// swp_fit_pairs: every pair goes to the owner of its node (a node never spans shards, so each shard's chain is the whole chain of its
+// nodes), the sub-lists keep the caller's order. All or nothing across the set: everything every shard would refuse is refused here
+// before the first shard runs; what is left to fail after that is the device itself.
+int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail) {
+    ShardSet& S = *e->set;
+    if ((!templates && n_templates) || (!pairs && n_pairs) || (!first_fail && n_pairs)) return SWP_EINVAL;
+    if (S.broken) return broken_error(e);
+    if (n_pairs == 0) return SWP_OK;
+    const swp_engine* c0 = S.sh[0];   // (predicate sets and ids are replicated: shard 0 speaks for all)
+    for (uint32_t t = 0; t < n_templates; ++t) {
+        const swp_task_desc& d = templates[t];
+        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+        if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
+        if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
+        if (d.service >= c0->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
+        if (d.constraint_set >= c0->con_sets.size() || d.platform_set >= c0->plat_sets.size() || d.plugin_set >= c0->plug_sets.size() ||
+            d.port_set >= c0->port_sets.size() || d.generic_set >= c0->gen_sets.size())
+            return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown predicate set", t);
+    }
+    std::vector<std::vector<swp_fit_pair>> per(S.sh.size());
+    std::vector<std::vector<uint32_t>> src(S.sh.size());
+    for (uint32_t i = 0; i < n_pairs; ++i) {
+        if (pairs[i].tmpl >= n_templates) return e->fail(SWP_EINVAL, "fit_pairs: pair %u names template %u of %u", i, pairs[i].tmpl, n_templates);
+        uint32_t g = 0, l = 0;
+        if (!locate(S, pairs[i].node, &g, &l) || l >= S.sh[g]->nodes.size() || !S.sh[g]->nodes[l].present)
+            return e->fail(SWP_ENOTFOUND, "fit_pairs: pair %u: node %u is not in the nodeSet mirror", i, pairs[i].node);
+        per[g].push_back(swp_fit_pair{l, pairs[i].tmpl});
+        src[g].push_back(i);
+    }
+    std::vector<int32_t> ff;
+    for (size_t g = 0; g < per.size(); ++g) {
+        if (per[g].empty()) continue;
+        ff.resize(per[g].size());
+        if (int rc = swp_fit_pairs(S.sh[g], templates, n_templates, per[g].data(), (uint32_t)per[g].size(), ff.data())) return take_error(e, S.sh[g], rc);
+        for (size_t k = 0; k < ff.size(); ++k) first_fail[src[g][k]] = ff[k];
+    }
+    return SWP_OK;
+}
+
 int enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks, uint8_t* out_reject) {
     ShardSet& S = *e->set;
     if ((!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
