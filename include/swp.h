@@ -546,8 +546,8 @@ typedef struct {
     uint32_t n_nodes, n_words, last_windows, last_static_classes;
     float    ms_classes, ms_scan, ms_resolve, ms_explain, ms_total;   /* last batch, SWP_CFG_PROFILE */
     uint32_t scan_launches, resolve_launches;
-    uint32_t last_resolver;     /* resolver kernel of the last batch: 105 = k_resolve5 exact mode, 5 = k_resolve5 over the scan's rows,
-                                   3 = k_resolve3, 2 = k_resolve2, 1 = k_resolve1, 0 = k_resolve */
+    uint32_t last_resolver;     /* resolver kernel of the last batch: 6 = k_resolve6 (block resolver), 7 = k_r7_* (node-range shards).
+                                   105 and 5 (the retired round resolver, k_resolve5) and 3, 2, 1, 0 (earlier resolvers) are no longer produced */
     /* node-range shard protocol, last batch (since swp_shard_begin); the times need SWP_CFG_PROFILE */
     float    ms_propose, ms_apply;          /* Σ k_propose / k_shard_apply launch durations */
     uint32_t propose_launches, propose_tasks;   /* launches and Σ tasks proposed (a task cut off a block is proposed again) */

@@ -11,10 +11,10 @@
 //
 // This header holds the kernels around the resolvers: predicate classes, the explain pass, the
 // event-handler residual updates, the enforcer sweep and the pair check. The sequential argmin + commit pass itself lives in
-// swp_resolve5.hpp (round resolver, node sets that fit one workgroup's LDS), swp_resolve6.hpp (block resolver, bitmap rows in
-// global memory), swp_waterfill.hpp (runs of identical tasks) and swp_shard.hpp (node-range shards). Why parallel kernels
-// reproduce the reference's strictly sequential tick (scheduler.go:464-469) — inside one batch feasibility only goes 1→0 and a
-// node's score (max(fail,4), svcCount, total, index) only grows — is argued in DESIGN.md §2.
+// swp_resolve6.hpp (block resolver, bitmap rows in global memory), swp_scan.hpp (scan resolver), swp_waterfill.hpp (runs of
+// identical tasks) and swp_shard.hpp (node-range shards). Why parallel kernels reproduce the reference's strictly sequential
+// tick (scheduler.go:464-469) — inside one batch feasibility only goes 1→0 and a node's score (max(fail,4), svcCount, total,
+// index) only grows — is argued in DESIGN.md §2.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -739,20 +739,6 @@ __global__ __launch_bounds__(256) void k_gather_rows(const u32* idx, const u32* 
 // k_commit — NodeInfo.addTask / removeTask arithmetic for placements decided outside the engine
 // (nodeinfo.go:66-154). Several placements may hit one node: integer atomics commute.
 // ---------------------------------------------------------------------------------------------
-// Residuals in the batch's resource units for k_resolve5: floor division, so that need <= residual <=> need/unit <= q for
-// every need that is a multiple of the unit (a negative residual fits nothing, not even a zero reservation: filter.go:78-84).
-__global__ void k_units(u32 n, const i64* __restrict__ cpu, const i64* __restrict__ mem, i64 uc, i64 um, int32_t* __restrict__ q) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    auto fd = [](i64 a, i64 b) {
-        i64 d = a / b;
-        if (a % b != 0 && a < 0) --d;
-        return d < -(1ll << 30) ? -(1ll << 30) : d > (1ll << 30) ? (1ll << 30) : d;   // present nodes are range-checked by the host
-    };
-    q[2 * i] = (int32_t)fd(cpu[i], uc);
-    q[2 * i + 1] = (int32_t)fd(mem[i], um);
-}
-
 // k_scatter_rows — the rows swp_node_update_dynamic changed (flush_nodes): flags word, residuals, task count of each
 struct DevRow {
     u32 node, flags, total, pad;

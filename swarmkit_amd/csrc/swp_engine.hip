@@ -17,7 +17,6 @@
 #include <tuple>
 #include <queue>
 #include <mutex>
-#include <numeric>
 #include <memory>
 #include <set>
 #include <string>
@@ -417,16 +416,10 @@ struct swp_batch {
     uint32_t n_con = 0, n_plat = 0, n_plug = 0, n_sc = 0, n_svc = 0, n_ports = 0;
     uint32_t n_nodes_prepared = 0;         // e->n_nodes when the batch was prepared: its bitmap rows are sized for that
     bool ran = false;
-    int64_t unit_cpu = 1, unit_mem = 1;   // k_resolve5: gcd of the batch's reservations (RTask.kc / km count these units)
-    bool units_ok = false;                // every reservation fits 2^30 units
-    // k_resolve5 exact mode: the distinct cpu / memory reservations of the batch as demand classes (RTask.flags carries the
-    // class indices); usable when they fit R5's row budget
-    std::vector<int32_t> thr;
-    uint32_t n_dc = 0, n_dm = 0;
-    bool exact_ok = false;
-    // k_resolve6 (block resolver): the same classes with the thresholds in raw units (NanoCPUs / bytes); usable whenever the
-    // class indices fit the 8 bits RTask.flags has for each
+    // k_resolve6 (block resolver): the distinct cpu / memory reservations of the batch as demand classes, thresholds in raw
+    // units (NanoCPUs / bytes; RTask.flags carries the class indices); usable whenever the indices fit RTask.flags' bits
     std::vector<int64_t> thr64;
+    uint32_t n_dc = 0, n_dm = 0;
     bool classes_ok = false;
     // generic reservations (filter.go:86-91): the distinct (kind, value) pairs of the batch's tasks are more demand-class rows,
     // rg[r] = {count[kind_r] >= value_r}, sorted by (kind, value); a task names the rows of its set
@@ -460,8 +453,6 @@ struct swp_batch {
     std::vector<XGroup> xg_proto;    // the groups (off / cnt / doff filled per run; pad = reservation pair)
     uint32_t xg_pairs = 0;
     std::vector<uint32_t> hx_fill, hx_pair_cnt, hx_compact;
-    DevBuf d_qres;                         // k_resolve5: [n_nodes][2] residuals in resource units
-    DevBuf d_thr;                          // k_resolve5 exact mode: thresholds of the demand-class rows
     DevBuf d_trows;                        // k_resolve6, task-rows mode: [block][n_words]
     DevBuf d_thr64, d_planes6, d_rr6, d_blk6;   // k_resolve6: raw thresholds, level planes, demand-class rows, control block
     // segments of the batch: runs of identical tasks (k_waterfill) and the stretches between them (the resolvers)
@@ -1063,52 +1054,28 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
         task_rank[i] = svc_ntasks[r.svc];
         svc_ntasks[r.svc] += weights ? weights[i] : 1u;
     }
-    // resource units of the round resolver: residual fits(need) <=> need/unit <= floor(residual/unit) when every need is a
-    // multiple of the unit, so the kernel can keep exact residuals as 32-bit counts in LDS
+    // demand classes: ResourceFilter (filter.go:77-84) becomes membership in two bitmap rows per task — the distinct cpu /
+    // memory reservations of the batch, ascending; RTask.flags carries the task's two row indices (k_resolve6 keeps the rows
+    // in global memory).
+    b->classes_ok = false;
+    b->thr64.clear();
+    b->n_dc = b->n_dm = 0;
     {
-        int64_t gc = 0, gm = 0;
-        for (uint32_t i : firsts) {
-            gc = std::gcd(gc, b->rt[i].cpu);
-            gm = std::gcd(gm, b->rt[i].mem);
-        }
-        b->unit_cpu = gc ? gc : 1;
-        b->unit_mem = gm ? gm : 1;
-        b->units_ok = true;
-        for (uint32_t i : firsts) {
-            const int64_t kc = b->rt[i].cpu / b->unit_cpu, km = b->rt[i].mem / b->unit_mem;
-            if (kc >= R5_QLIM_HOST || km >= R5_QLIM_HOST) { b->units_ok = false; break; }
-            b->rt[i].kc = (uint32_t)kc;
-            b->rt[i].km = (uint32_t)km;
-        }
-        // demand classes: ResourceFilter (filter.go:77-84) becomes membership in two bitmap rows per task — the distinct cpu /
-        // memory reservations of the batch, ascending; RTask.flags carries the task's two row indices. k_resolve5's exact mode
-        // keeps the rows in LDS (thresholds in resource units, at most r5_max_rows() of them), k_resolve6 in global memory.
-        b->exact_ok = b->classes_ok = false;
-        b->thr.clear();
-        b->thr64.clear();
-        b->n_dc = b->n_dm = 0;
-        {
-            std::set<int64_t> sc_, sm_;
-            for (uint32_t i : firsts)
-                if (b->rt[i].flags & RT_RES) {
-                    sc_.insert(b->rt[i].cpu);
-                    sm_.insert(b->rt[i].mem);
-                }
-            if (sc_.size() <= RT_DCLS_MASK && sm_.size() <= RT_DCLS_MASK) {
-                std::unordered_map<int64_t, uint32_t> ic, im;
-                for (int64_t v : sc_) { ic[v] = (uint32_t)b->thr64.size(); b->thr64.push_back(v); }
-                b->n_dc = (uint32_t)sc_.size();
-                for (int64_t v : sm_) { im[v] = (uint32_t)b->thr64.size() - b->n_dc; b->thr64.push_back(v); }
-                b->n_dm = (uint32_t)sm_.size();
-                for (uint32_t i : firsts)
-                    if (b->rt[i].flags & RT_RES) b->rt[i].flags |= (ic[b->rt[i].cpu] << RT_DC_SHIFT) | (im[b->rt[i].mem] << RT_DM_SHIFT);
-                b->classes_ok = true;
-                if (b->units_ok && b->n_dc + b->n_dm <= r5_max_rows()) {   // the same order in resource units (division by the gcd is monotone)
-                    for (uint32_t c = 0; c < b->n_dc; ++c) b->thr.push_back((int32_t)(b->thr64[c] / b->unit_cpu));
-                    for (uint32_t c = 0; c < b->n_dm; ++c) b->thr.push_back((int32_t)(b->thr64[b->n_dc + c] / b->unit_mem));
-                    b->exact_ok = true;
-                }
+        std::set<int64_t> sc_, sm_;
+        for (uint32_t i : firsts)
+            if (b->rt[i].flags & RT_RES) {
+                sc_.insert(b->rt[i].cpu);
+                sm_.insert(b->rt[i].mem);
             }
+        if (sc_.size() <= RT_DCLS_MASK && sm_.size() <= RT_DCLS_MASK) {
+            std::unordered_map<int64_t, uint32_t> ic, im;
+            for (int64_t v : sc_) { ic[v] = (uint32_t)b->thr64.size(); b->thr64.push_back(v); }
+            b->n_dc = (uint32_t)sc_.size();
+            for (int64_t v : sm_) { im[v] = (uint32_t)b->thr64.size() - b->n_dc; b->thr64.push_back(v); }
+            b->n_dm = (uint32_t)sm_.size();
+            for (uint32_t i : firsts)
+                if (b->rt[i].flags & RT_RES) b->rt[i].flags |= (ic[b->rt[i].cpu] << RT_DC_SHIFT) | (im[b->rt[i].mem] << RT_DM_SHIFT);
+            b->classes_ok = true;
         }
     }
     mark("templates + first records");
@@ -1200,7 +1167,7 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
     mark("explain groups");
     // runs of identical one-off tasks (same service, filters, reservations; only their list slot differs) are placed by
     // water-filling instead of task by task (csrc/swp_waterfill.hpp). A run must be long enough to pay for its launch, and
-    // splitting the batch must not shred the round resolver's work into many launches: runs are used when they make up most
+    // splitting the batch must not shred the resolver's work into many launches: runs are used when they make up most
     // of the batch or one of them is long. SWP_WATERFILL=0 switches them off, =1 forces every run of 2 or more (tests).
     b->segs.clear();
     {
@@ -1387,7 +1354,6 @@ int upload_batch(swp_engine* e, swp_batch* b) {
         HIPCHECK(e, b->d_vrows.reserve(b->csi_set.size() * (size_t)std::max<uint32_t>(Wn, 1) * 8));
         HIPCHECK(e, b->d_att.reserve(b->csi_set.size() * (size_t)SWP_MAX_MOUNTS * 4));
     }
-    if ((rc = stage(b->d_thr, b->thr))) return rc;
     if ((rc = stage(b->d_thr64, b->thr64))) return rc;
     if (b->has_generic) {
         if ((rc = stage(b->d_tg, b->tg))) return rc;
@@ -1857,32 +1823,11 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
     if (prof) HIPCHECK(e, hipEventRecord(e->ev[1], st));
 
     const size_t lds_budget = 160 * 1024 - 512;
-    // Two resolver families. k_resolve5, the ROUND resolver: everything it decides from lives in one workgroup's LDS (<= ~12 000
-    // nodes, the batch's distinct reservations as at most r5_max_rows() demand-class rows, residuals as 32-bit counts of the
-    // batch's resource units) — one launch per batch. k_resolve6, the BLOCK resolver: bitmap rows in global memory, lists built by
-    // the whole chip — everything else. Test / debugging knobs, read once per batch: SWP_RESOLVER=5|6 forces a family
-    // (tests/test_engine_resolvers.py), SWP_DBG bit 16 switches the in-kernel section timers on.
-    const char* env_res = getenv("SWP_RESOLVER");
+    // k_resolve6, the BLOCK resolver: lists built by the whole chip from bitmap rows in global memory, matched by one wave. Needs the
+    // demand classes and two candidate buffers of the propose kernel in LDS (≈ 650k nodes). Test / debugging knobs, read once per
+    // batch: SWP_R6_BLOCK sets the tasks per round, SWP_DBG bit 16 switches the in-kernel section timers on.
     const char* env_dbg = getenv("SWP_DBG");
     const uint32_t dbg_bits = env_dbg ? (uint32_t)atoi(env_dbg) : 0u;
-    // (without the knob: the block resolver. Round 4 measured it ahead of the round resolver at EVERY batch size on 10 000 nodes — 0.21 vs
-    // 0.54 ms for 256 tasks, 1.1 vs 1.5 ms for 8 192, 12.8 vs 14.9 ms for 100 000 — and twice as fast on the churn rounds, whose ~9 000
-    // re-placements all aim at the few emptied nodes (profiles/r04_*). The round resolver stays as the family that needs no bitmaps:
-    // SWP_RESOLVER=5, and the fall-back below.)
-    int variant = env_res ? atoi(env_res) : 6;
-    if (variant != 5 && variant != 6) return e->fail(SWP_EINVAL, "SWP_RESOLVER=%d: the resolver families are 5 (round) and 6 (block)", variant);
-    if (!b->csi_set.empty()) variant = 6;   // tasks with cluster mounts: the block resolver knows the volumes
-    const size_t r5_lds = r5_lds_size(N, Wn, b->exact_ok ? b->n_dc + b->n_dm : 0u);
-    bool r5_ok = b->exact_ok && b->units_ok && r5_supports(Wn) && r5_lds <= lds_budget && !b->has_generic && b->csi_set.empty();
-    for (uint32_t n = 0; r5_ok && n < N; ++n) {
-        const HostNode& h = e->nodes[n];
-        if (!h.present) continue;
-        const int64_t qc = h.row.cpu / b->unit_cpu, qm = h.row.mem / b->unit_mem;
-        if (qc >= R5_QLIM_HOST || qc <= -R5_QLIM_HOST || qm >= R5_QLIM_HOST || qm <= -R5_QLIM_HOST) r5_ok = false;
-    }
-    // k_resolve6 (block resolver): lists built by the whole chip from bitmap rows in global memory, matched by one wave. For node
-    // sets beyond k_resolve5's LDS; needs the demand classes and two candidate buffers of the propose kernel in LDS (≈ 650k nodes).
-    // SWP_RESOLVER=6 forces it at any size; SWP_R6_BLOCK sets the tasks per round.
     const char* env_blk = getenv("SWP_R6_BLOCK");
     // (without the knob: as many 64-task groups as the commit kernel's LDS holds next to the TK row, at most R6_BLOCK_DEFAULT_CAP tasks)
     uint32_t r6_block = std::min<uint32_t>(r6_block_max(), std::max<uint32_t>(1u, env_blk ? (uint32_t)atoi(env_blk) : R6_BLOCK_DEFAULT_CAP));
@@ -1894,16 +1839,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
     // (the commit kernel stages the block's lists in LDS next to the TK row: a very large node set gets a smaller block)
     while (r6_block > 64 && r6_commit_lds_size(Wn, r6_block, r6_nrr) > lds_budget) r6_block = (r6_block - 1u) / 64u * 64u;
     const bool r6_ok = r6_propose_lds_size(Wn) <= lds_budget && r6_commit_lds_size(Wn, r6_block, r6_nrr) <= lds_budget && Wn <= 32768u;   // (half-word indices of 16 bits in the commit kernel's LDS)
-    if (variant == 5 && !r5_ok) variant = 6;
-    if (variant == 6 && !r6_ok) {
-        if (r5_ok) variant = 5;   // (a node set whose rows leave the block resolver no LDS but fits the round resolver's: cannot happen with today's limits)
-        else return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", N);
-    }
-    if (variant == 5) {
-        HIPCHECK(e, b->d_qres.reserve((size_t)N * 8));
-        hipLaunchKernelGGL(k_units, dim3((N + 255) / 256), dim3(256), 0, st, N, e->d_cpu.as<long long>(), e->d_mem.as<long long>(), (long long)b->unit_cpu,
-                           (long long)b->unit_mem, b->d_qres.as<int32_t>());
-    }
+    if (!r6_ok) return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", N);
     uint32_t wi = 0;   // resolver stretches launched so far (profiling slots)
     uint64_t r6_rounds = 0;
     // k_resolve6 over the stretch [start, end): build the bitmaps from the node rows as they are, then rounds of propose + commit.
@@ -2074,67 +2010,12 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
         }
         return SWP_OK;
     };
-    // one stretch of tasks through the chosen family: the round resolver decides it in ONE launch
-    auto run_stretch = [&](uint32_t start, uint32_t end, int variant) -> int {
-        if (variant == 6) return run_blocks(start, end);
-        if (prof)
-            while (e->ev_pool.size() < (size_t)4 * (wi + 1)) {
-                hipEvent_t x;
-                HIPCHECK(e, hipEventCreate(&x));
-                e->ev_pool.push_back(x);
-            }
-        ResolveArgs ra{};
-        ra.n_nodes = N;
-        ra.n_words = Wn;
-        ra.j0 = start;
-        ra.count = end - start;
-        ra.dbg = dbg_bits;
-        ra.xs = Wn;
-        ra.valid = e->d_valid.as<u64>();
-        ra.X = b->d_X.as<u64>();
-        ra.rt = b->d_rt.as<RTask>();
-        ra.cpu = e->d_cpu.as<long long>();
-        ra.mem = e->d_mem.as<long long>();
-        ra.total = e->d_total.as<uint32_t>();
-        ra.list_node = b->d_list_node.as<uint32_t>();
-        ra.list_svc = b->d_list_svc.as<uint32_t>();
-        ra.list_fail = b->d_list_fail.as<uint32_t>();
-        ra.list_off = b->d_list_off.as<uint32_t>();
-        ra.portmap = b->d_portmap.as<u64>();
-        ra.pset_off = b->d_pset_off.as<uint32_t>();
-        ra.pset_ids = b->d_pset_ids.as<uint32_t>();
-        ra.out_node = b->d_out.as<int32_t>();
-        ra.log_node = b->d_log_node.as<uint32_t>();
-        ra.log_task = b->d_log_task.as<uint32_t>();
-        ra.log_prev = b->d_log_prev.as<int32_t>();
-        ra.last = b->d_last.as<int32_t>();
-        ra.inf_task = b->d_inf_task.as<uint32_t>();
-        ra.inf_pos = b->d_inf_pos.as<uint32_t>();
-        ra.ctl = b->d_ctl.as<Ctl>();
-        ra.qres = b->d_qres.as<int32_t>();
-        ra.unit_cpu = b->unit_cpu;
-        ra.unit_mem = b->unit_mem;
-        ra.sc = b->d_sc.as<u64>();
-        ra.thr = b->d_thr.as<int32_t>();
-        ra.n_dc = b->n_dc;
-        ra.n_dm = b->n_dm;
-        if (prof) {
-            HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 0], st));
-            HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 1], st));
-            HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 2], st));
-        }
-        const hipError_t r = launch_resolve5(ra, r5_lds, st, e->device);
-        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_resolve5 launch: %s", hipGetErrorString(r));
-        if (prof) HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 3], st));
-        ++wi;
-        return SWP_OK;
-    };
-    if (b->segs.empty()) rc = run_stretch(0, T, variant);
+    if (b->segs.empty()) rc = run_blocks(0, T);
     else {
         HIPCHECK(e, b->d_wf.reserve((size_t)3 * N * 4));
         for (const swp_batch::Seg& sg : b->segs) {
             if (!sg.run) {
-                if ((rc = run_stretch(sg.j0, sg.j0 + sg.n, variant))) break;
+                if ((rc = run_blocks(sg.j0, sg.j0 + sg.n))) break;
                 continue;
             }
             WaterArgs wa{};
@@ -2161,7 +2042,6 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
             wa.inf_task = b->d_inf_task.as<uint32_t>();
             wa.inf_pos = b->d_inf_pos.as<uint32_t>();
             wa.ctl = b->d_ctl.as<Ctl>();
-            wa.qres = variant == 5 ? b->d_qres.as<int32_t>() : nullptr;
             wa.ps = b->d_wf.as<uint32_t>();
             wa.cap = wa.ps + N;
             wa.ent = wa.cap + N;
@@ -2176,18 +2056,6 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
     Ctl ctl{};
     HIPCHECK(e, hipMemcpyAsync(&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
     HIPCHECK(e, hipStreamSynchronize(st));
-    if (ctl.error == ERR_LEVEL_RANGE && variant == 5 && r6_ok && ctl.resume < T) {
-        // The per-node task-count spread outgrew the 8 level planes the round resolver keeps in LDS (255 levels). It stopped cleanly
-        // after task `resume` - 1 and every later launch returned at once: the block resolver (16 planes in global memory) carries
-        // on from there — runs of identical tasks included, task by task.
-        const uint32_t zero = 0;
-        HIPCHECK(e, hipMemcpyAsync((char*)b->d_ctl.p + offsetof(Ctl, error), &zero, 4, hipMemcpyHostToDevice, st));
-        variant = 6;
-        rc = run_stretch(ctl.resume, T, 6);
-        if (rc) return rc;
-        HIPCHECK(e, hipMemcpyAsync(&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIPCHECK(e, hipStreamSynchronize(st));
-    }
     if (prof) HIPCHECK(e, hipEventRecord(e->ev[2], st));
     if (ctl.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the resolvers' level planes");
     if (ctl.ninf && (rc = run_explain(e, b, ctl.ninf))) return rc;
@@ -2223,35 +2091,17 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
     e->stats.rebase_events += ctl.rebases;
     e->stats.generic_tasks += ctl.generic_tasks;
     e->stats.resolver_spins += ctl.spin_waits;
-    if ((dbg_bits & 16) && variant == 5)
-        fprintf(stderr, "[swp] k_resolve5: rounds %llu (full %llu, cut by class %llu, cut by an exhausted list %llu) | commits %u inf %u generic-path tasks %llu retries %llu\n",
-                ctl.cyc[0], ctl.cyc[1], ctl.cyc[2], ctl.cyc[3], ctl.ncommit, ctl.ninf, ctl.generic_tasks, ctl.verify_retries);
-    if ((dbg_bits & 16) && variant == 5) {
-        auto lo = [](unsigned long long v) { return (double)(v & 0xFFFFFFFFull) * 64.0; };
-        auto hi = [](unsigned long long v) { return (double)(v >> 32) * 64.0; };
-        const double r = ctl.cyc[0] ? (double)ctl.cyc[0] : 1.0;
-        fprintf(stderr, "[swp] k_resolve5 shader cycles per round: wave0 match %.0f barrier1 %.0f commit %.0f barrier2 %.0f | wave1 list %.0f barrier1 %.0f idle %.0f barrier2 %.0f | cut/refill/generic %.0f\n",
-                lo(ctl.cyc[4]) / r, hi(ctl.cyc[4]) / r, lo(ctl.cyc[5]) / r, hi(ctl.cyc[5]) / r, lo(ctl.cyc[6]) / r, hi(ctl.cyc[6]) / r, lo(ctl.cyc[7]) / r,
-                hi(ctl.cyc[7]) / r, (double)ctl.pad1 * 64.0 / r);
-        fprintf(stderr, "[swp] k_resolve5 matcher per round (cycles): list load %.0f, matching loop %.0f of which inside the scalar loop %.0f over %.1f entries\n", (double)ctl.m_cyc[0] * 64.0 / r, (double)ctl.m_cyc[1] * 64.0 / r,
-                (double)ctl.m_cyc[2] * 64.0 / r, (double)ctl.m_cyc[3] / r);
-fprintf(stderr, "[swp] k_resolve5 lister wave 1 per round (cycles): prologue %.0f | per 4 tasks: row wait %.0f, level search %.0f, entries %.0f, validation %.0f\n",
-                (double)ctl.l_cyc[0] * 64.0 / r, (double)ctl.l_cyc[1] * 64.0 / r, (double)ctl.l_cyc[2] * 64.0 / r, (double)ctl.l_cyc[3] * 64.0 / r, (double)ctl.l_cyc[4] * 64.0 / r);
-        fprintf(stderr, "[swp] k_resolve5 phase-1 work per wave and round (cycles):");
-        for (int w = 0; w < 16; ++w) fprintf(stderr, " %.0f", (double)ctl.wave_cyc[w] * 64.0 / r);
-        fprintf(stderr, "\n");
-    }
-    else if (dbg_bits & 16)
+    if (dbg_bits & 16)
         fprintf(stderr, "[swp] resolver cycles (100MHz ticks): wait %llu prep %llu pick %llu generic %llu commit %llu blockend %llu | commits %u inf %u generic %llu\n",
                 ctl.cyc[0], ctl.cyc[1], ctl.cyc[2], ctl.cyc[3], ctl.cyc[4], ctl.cyc[5], ctl.ncommit, ctl.ninf, ctl.generic_tasks);
     if ((dbg_bits & 16) && ctl.cyc[7])
         fprintf(stderr, "[swp] shader clock: %llu cycles / %llu x10ns => %.0f MHz\n", ctl.cyc[6], ctl.cyc[7], (double)ctl.cyc[6] / ((double)ctl.cyc[7] * 0.01));
     e->stats.scan_launches = e->scan_stretches_batch;
     e->stats.scan_tasks = e->scan_tasks_batch;
-    e->stats.last_windows = wi;   // resolver launches of this batch (1 in k_resolve5's exact mode: no scan windows)
+    e->stats.last_windows = wi;   // resolver stretches of this batch
     e->stats.last_static_classes = b->n_sc;
-    e->stats.resolve_launches += variant == 6 ? (uint32_t)(2 * r6_rounds) : wi;   // k_resolve6: a propose and a commit launch per round
-    e->stats.last_resolver = variant == 5 ? 105u : 6u;   // 105 = k_resolve5 (its demand-class rows in LDS), 6 = k_resolve6
+    e->stats.resolve_launches += (uint32_t)(2 * r6_rounds);   // k_resolve6: a propose and a commit launch per round
+    e->stats.last_resolver = 6u;   // k_resolve6
     b->ran = true;
     return SWP_OK;
 }

@@ -6,17 +6,9 @@
 
 namespace swpdev {
 
-#define R5_QLIM_HOST (1ll << 30)   // residuals / reservations in resource units must stay below this (== R5_QLIM)
-
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE setting: remembered per (kernel, device ordinal), so
 // that a process holding engines on several GPUs (a manager sharding over the node's 8 devices) raises the limit on each.
 hipError_t ensure_big_lds(const void* fn, int device);
-
-// k_resolve5 (swp_resolve5.hip)
-size_t r5_lds_size(uint32_t n_nodes, uint32_t n_words, uint32_t n_rr);   // n_rr: demand-class rows
-uint32_t r5_max_rows();
-bool r5_supports(uint32_t n_words);
-hipError_t launch_resolve5(const ResolveArgs& ra, size_t lds, hipStream_t s, int dev);
 
 // k_resolve6, the block resolver (swp_resolve6.hip)
 struct R6Args;

@@ -1,6 +1,6 @@
 // swp_resolve6.hpp — the BLOCK resolver: the sequential argmin + commit pass of the tick (nodeSet.tree with a heap of one,
 // nodeset.go:50-124; nodeLess, scheduler.go:708-735; NodeInfo.addTask, nodeinfo.go:108-154). The whole chip builds the candidate
-// lists, one wave matches them. The engine's default from 16 384 tasks on and for every node set beyond k_resolve5's LDS.
+// lists, one wave matches them. The engine's resolver for a one-off batch on a single engine, at every batch size.
 //
 // State in global memory (L2-resident), all of it bitmaps over the node words, kept exact by every commit:
 //   planes[b]   bit b of (ActiveTasksCount − base) per node, base = the lowest count among the valid nodes at build time

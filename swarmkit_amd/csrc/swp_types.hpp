@@ -1,5 +1,5 @@
-// swp_types.hpp — plain C++ records shared by the kernels (swp_device.hpp, swp_resolve5.hpp), the engine runtime
-// (swp_engine.hip) and the CPU emulation harness of the round resolver (tests/emu/). No HIP types in here.
+// swp_types.hpp — plain C++ records shared by the kernels (swp_device.hpp, swp_resolve6.hpp, ...), the engine runtime
+// (swp_engine.hip) and the CPU emulation harnesses (tests/emu/). No HIP types in here.
 #pragma once
 #include <stdint.h>
 
@@ -28,8 +28,8 @@ typedef uint32_t u32;
 #define RT_PORTS 0x2u      // host-port filter enabled
 #define RT_MAXREP 0x4u     // max-replicas filter enabled
 #define RT_UNCOUNTED 0x8u  // DesiredState > COMPLETED: placement does not bump the task counts
-// The task's demand classes (index into the batch's sorted distinct cpu / memory reservations: ResolveArgs.thr in k_resolve5's
-// exact mode, R6Args.thr in the block resolver) ride in the flag word. Meaningful only with RT_RES.
+// The task's demand classes (index into the batch's sorted distinct cpu / memory reservations, R6Args.thr in the block
+// resolver) ride in the flag word. Meaningful only with RT_RES.
 #define RT_DC_SHIFT 8
 #define RT_DM_SHIFT 20
 #define RT_DCLS_MASK 0xFFFu   // 12 bits each: up to 4 095 distinct cpu and 4 095 distinct memory reservations per batch
@@ -47,7 +47,7 @@ struct RTask {   // 64 B per task, batch order
     u32 pset;      // batch-local port set
     u32 cls_con, cls_plat, cls_plug;   // batch-local class rows (0 = filter disabled) — explain pass
     u64 maxrep;
-    u32 kc, km;    // k_resolve5: the reservations in the batch's resource units (cpu = kc * unit_cpu, mem = km * unit_mem)
+    u32 kc, km;    // unused padding (no kernel reads them): keeps the record at 64 B with the offsets the kernels read
 };
 static_assert(sizeof(RTask) == 64, "RTask layout");
 
@@ -61,48 +61,11 @@ struct Ctl {
     u32 ncommit, ninf, error, resume;   // resume: first task NOT processed when `error` stopped a resolver (host continues from there)
     u64 verify_retries, slow_tasks, rebases, generic_tasks, spin_waits, pad1;
     u64 cyc[8];   // dbg&16: cycles spent in resolver sections
-    u64 m_cyc[4];       // dbg&16, k_resolve5 matcher: list load / matching loop / flush, units of 64 cycles
-    u64 l_cyc[8];       // dbg&16, k_resolve5 lister wave 1: sections of r5_list, units of 64 cycles
-    u64 wave_cyc[16];   // dbg&16, k_resolve5: per wave, cycles of work in phase 1 (match / list / memory commit), units of 64
+    u64 m_cyc[4];       // k_groups2's section timers (SWP_G2_PROF build, SWP_DBG=16): inside the walk
+    u64 l_cyc[8];       // k_groups2's section timers: further sections
+    u64 wave_cyc[16];   // k_groups2's section timers: per-section counts and cycles (admission, sort, candidate batches)
 };
 
 enum { ERR_NONE = 0, ERR_LEVEL_RANGE = 1, ERR_GROUP_RANGE = 2 };
-
-// arguments of the round resolver (k_resolve5, swp_resolve5.hpp); one launch = one stretch of the batch's tasks
-struct ResolveArgs {
-    u32 n_nodes, n_words;
-    u32 j0, count;           // the stretch: tasks [j0, j0 + count) of the batch
-    u32 dbg;                 // timing experiments only (env SWP_DBG); 0 in production
-    u32 xs;                  // row stride of X in words
-    const u64* valid;        // [n_words]
-    u64* X;                  // [n_svc][n_words]
-    const RTask* rt;
-    i64* cpu;
-    i64* mem;
-    u32* total;
-    u32* list_node;
-    u32* list_svc;
-    u32* list_fail;
-    const u32* list_off;     // [n_svc+1]
-    u64* portmap;
-    const u32* pset_off;
-    const u32* pset_ids;
-    int32_t* out_node;       // [T]
-    u32* log_node;
-    u32* log_task;
-    int32_t* log_prev;
-    int32_t* last;           // [n_nodes]
-    u32* inf_task;
-    u32* inf_pos;
-    Ctl* ctl;
-    int32_t* qres;           // [n_nodes][2] residual cpu / mem in the batch's resource units (floor division)
-    i64 unit_cpu, unit_mem;  // the units (RTask.cpu == kc * unit_cpu, RTask.mem == km * unit_mem)
-    // Feasibility of a plain task is sc[task's static class] & RC[its cpu class] & RM[its memory class], where the demand-class
-    // rows live in LDS and are kept exact by every commit (a node's bit leaves a row when its residual drops below the row's
-    // threshold).
-    const u64* sc;           // [n_sc][n_words] static class rows (ready & constraint & platform & plugin)
-    const int32_t* thr;      // [n_dc + n_dm] thresholds in resource units: the distinct cpu reservations, then the memory ones
-    u32 n_dc, n_dm;
-};
 
 }  // namespace swpdev

@@ -41,7 +41,6 @@ struct WaterArgs {
     u32* inf_task;
     u32* inf_pos;
     Ctl* ctl;
-    int32_t* qres;           // residuals in resource units (k_resolve5's), or nullptr
     u32* ps;                 // scratch [n_nodes]: failure class << 24 | svcCount; 0xFFFFFFFF = not in the game
     u32* cap;                // scratch [n_nodes]: tasks the node can still take
     u32* ent;                // scratch [n_nodes]: the node's entry in the service's exception list, or LIST_EMPTY
@@ -156,10 +155,6 @@ __global__ __launch_bounds__(WF_THREADS) void k_waterfill(WaterArgs a) {
                 const u64 bit = 1ull << (n & 63);
                 if (r.cpu) a.cpu[n] -= r.cpu;
                 if (r.mem) a.mem[n] -= r.mem;
-                if (a.qres) {
-                    a.qres[2 * n] -= (int32_t)r.kc;
-                    a.qres[2 * n + 1] -= (int32_t)r.km;
-                }
                 a.total[n] = (u32)v + 1;
                 const u32 e = a.ent[n];
                 if (e == LIST_EMPTY) {   // first task of the service here: the node joins its exception list (this task's own slot)

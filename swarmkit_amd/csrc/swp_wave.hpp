@@ -1,10 +1,11 @@
-// swp_wave.hpp — the wave64 / workgroup primitives the round resolver (swp_resolve5.hpp) is written against, gfx950 build.
+// swp_wave.hpp — the wave64 / workgroup primitives the resolvers (swp_resolve6.hpp, swp_resolve7.hpp, swp_scan.hpp) and task
+// groups (swp_groups.hpp) are written against, gfx950 build.
 //
 // The kernel source uses ONLY these wrappers for everything that is not plain C++ on registers and pointers
 // (cross-lane traffic, LDS / global atomics, barriers, uniform loads). tests/emu/wv_emu.hpp implements the same
-// interface on CPU fibers, so the kernel's control flow, indexing and protocol can be run against a sequential model
-// without a GPU (tests/test_emu_resolve5.py). That harness is test infrastructure: the product only ever builds this
-// header. Rule the kernel follows so that both agree: collectives (ballot, readlane, min, barrier) are only called
+// interface on CPU fibers, so the kernels' control flow, indexing and protocol can be run against a sequential model
+// without a GPU (tests/test_emu_*.py). That harness is test infrastructure: the product only ever builds this
+// header. Rule the kernels follow so that both agree: collectives (ballot, readlane, min, barrier) are only called
 // from wave-uniform control flow.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -101,10 +102,7 @@ WV_DEV void lockstep() { asm volatile("" ::: "memory"); }
 WV_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ---- LDS atomics (no return value: nothing to wait for) ----
-WV_DEV void lds_or64(u64* p, u64 v) { __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-WV_DEV void lds_xor64(u64* p, u64 v) { __hip_atomic_fetch_xor(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV void lds_or32(u32* p, u32 v) { __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-WV_DEV void lds_andn64(u64* p, u64 v) { __hip_atomic_fetch_and(p, ~v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV void lds_min64(u64* p, u64 v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 // a read behind a barrier, not to be merged with an earlier one: the compiler fence does that — a `volatile` access would lose the
 // pointer's address space and come out as a FLAT load with a wait of its own (found in k_scanb: four of them in a row, ~2 000 cycles a batch)
@@ -130,18 +128,15 @@ WV_DEV void spin_pause() { __builtin_amdgcn_s_sleep(8); }   // ~0.2 µs off the 
 // coherence it needs: the operations stay in this XCD's L2 (device scope would send every load past it, ~1 µs each).
 // What other kernels wrote is visible from the launch on, what this one writes at its end.
 WV_DEV void g_add64(i64* p, i64 v) { __hip_atomic_fetch_add(reinterpret_cast<u64*>(p), (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-WV_DEV void g_add32(u32* p, u32 v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV void g_or64(u64* p, u64 v) { __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV void g_min64(u64* p, u64 v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV void g_xor64(u64* p, u64 v) { __hip_atomic_fetch_xor(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 WV_DEV void g_andn64(u64* p, u64 v) { __hip_atomic_fetch_and(p, ~v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 WV_DEV void g_max32(u32* p, u32 v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-WV_DEV u32 g_exch32(u32* p, u32 v) { return __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 // loads that must see what other waves of this workgroup wrote through L2 (bypass the CU's vector L1)
 WV_DEV u64 g_fresh64(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV u32 g_fresh32(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV i64 g_fresh64s(const i64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-WV_DEV void g_store32_fresh(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 // pull the cache line at p into this XCD's L2. An ordinary load whose value the caller must consume (sum it up and hand the
 // sum to keep()): the compiler then orders the wait itself. (A bare global_load in inline asm returns into a register the
 // compiler believes free — the late write corrupted whatever lived there next: found by the 12 400-node scan-mode case.)
@@ -154,7 +149,7 @@ WV_DEV T uload(const T* p) {
     return *reinterpret_cast<const __attribute__((address_space(4))) T*>(reinterpret_cast<uintptr_t>(p));
 }
 
-// The matcher's walk (swp_resolve5.hpp, swp_resolve6.hpp, swp_resolve7.hpp), hand-scheduled: the serial chain of the whole engine.
+// The matcher's walk (swp_resolve6.hpp, swp_resolve7.hpp), hand-scheduled: the serial chain of the whole engine.
 // Round 2's version was a scalar loop of 17 instructions per task over a mask of lanes still to serve (s_ff1 for the next lane, m0 as
 // the lane select of v_writelane); this one is unrolled over the 64 lanes.
 // Lane indices are immediates, so the scalar side no longer
@@ -234,7 +229,7 @@ WV_DEV u32 match_seq64(u32& bits, u32& w, u32& bits2, u32 w2, u32& pickb, u32 li
     return at;
 }
 
-// shader clock (s_memtime); used by the kernel's section timers when ResolveArgs.dbg & 16
+// shader clock (s_memtime); used by the kernels' section timers (SWP_DBG bit 16)
 WV_DEV u64 clock64() { return __builtin_amdgcn_s_memtime(); }
 
 WV_DEV int ffs64(u64 v) { return __ffsll((long long)v) - 1; }   // index of the lowest set bit (v != 0)

@@ -1,5 +1,5 @@
 // emu_model.hpp — random problems and the plain sequential restatement of the resolvers' semantics, shared by the CPU
-// emulation harnesses (emu_resolve5.cpp, emu_resolve6.cpp). TEST INFRASTRUCTURE; not part of the product.
+// emulation harnesses (emu_resolve6.cpp, emu_resolve7.cpp, emu_scan.cpp). TEST INFRASTRUCTURE; not part of the product.
 //
 // The model follows k_resolve (swp_device.hpp): plain nodes by (level, index) with a re-check of the dynamic filters, then the
 // service's exception list by nodeLess, scheduler.go:708-735; NodeInfo.addTask, nodeinfo.go:108-154.
@@ -49,8 +49,6 @@ struct State {   // everything a resolver mutates or emits
     std::vector<int32_t> gcnt;
     Ctl ctl{};
 };
-
-static i64 floordiv(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 static Problem make_problem(u32 seed, u32 N, u32 T, u32 S, int order, int feat) {
     std::mt19937_64 g(seed);
@@ -123,10 +121,8 @@ static Problem make_problem(u32 seed, u32 N, u32 T, u32 S, int order, int feat) 
         r.svc = s;
         r.sc = sv[s].sc;
         r.flags = sv[s].flags;
-        r.kc = sv[s].kc;
-        r.km = sv[s].km;
-        r.cpu = (i64)r.kc * p.UC;
-        r.mem = (i64)r.km * p.UM;
+        r.cpu = (i64)sv[s].kc * p.UC;
+        r.mem = (i64)sv[s].km * p.UM;
         r.pset = sv[s].pset;
         r.maxrep = sv[s].maxrep;
         rank[j] = ntasks[s]++;

@@ -3,9 +3,9 @@
 // TEST INFRASTRUCTURE. One workgroup is run as cooperative fibers (ucontext), one per thread; a collective (ballot,
 // readlane, min, wave_sync, barrier) parks the calling fiber until all 64 lanes of its wave (all threads of the
 // workgroup for a barrier) have arrived at the SAME collective, then the last arriver computes the result and releases
-// the others. That is enough to run the round resolver's source (swp_resolve5.hpp) unchanged and check its control
-// flow, indexing and hand-shakes against a sequential model — not its timing, and not memory-ordering hazards between
-// waves (fibers switch only at collectives). The product never includes this file.
+// the others. That is enough to run the kernels' source (swp_resolve6.hpp, swp_resolve7.hpp, swp_scan.hpp, swp_groups.hpp)
+// unchanged and check their control flow, indexing and hand-shakes against a sequential model — not their timing, and not
+// memory-ordering hazards between waves (fibers switch only at collectives). The product never includes this file.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -375,27 +375,21 @@ inline void lds_publish32(u32* p, u32 v) { *reinterpret_cast<volatile u32*>(p) =
 inline u32 lds_poll32(const u32* p) { return *reinterpret_cast<const volatile u32*>(p); }
 template <int P> inline void setprio() {}
 inline void spin_pause() { emu::yield_until_publish(); }
-inline void lds_or64(u64* p, u64 v) { *p |= v; }
-inline void lds_xor64(u64* p, u64 v) { *p ^= v; }
 inline void lds_or32(u32* p, u32 v) { *p |= v; }
-inline void lds_andn64(u64* p, u64 v) { *p &= ~v; }
 inline void lds_add32(u32* p, u32 v) { *p += v; }
 inline void lds_min64(u64* p, u64 v) { if (v < *p) *p = v; }
 inline u64 lds_read64(const u64* p) { return *reinterpret_cast<const volatile u64*>(p); }
 inline void lds_add_release32(u32* p, u32 v) { *reinterpret_cast<volatile u32*>(p) += v; emu::wake_pollers(); }
 
 inline void g_add64(i64* p, i64 v) { *p += v; }
-inline void g_add32(u32* p, u32 v) { *p += v; }
 inline void g_or64(u64* p, u64 v) { *p |= v; }
 inline void g_min64(u64* p, u64 v) { if (v < *p) *p = v; }
 inline void g_xor64(u64* p, u64 v) { *p ^= v; }
 inline void g_andn64(u64* p, u64 v) { *p &= ~v; }
 inline void g_max32(u32* p, u32 v) { if (v > *p) *p = v; }
-inline u32 g_exch32(u32* p, u32 v) { u32 o = *p; *p = v; return o; }
 inline u64 g_fresh64(const u64* p) { return *p; }
 inline u32 g_fresh32(const u32* p) { return *p; }
 inline i64 g_fresh64s(const i64* p) { return *p; }
-inline void g_store32_fresh(u32* p, u32 v) { *p = v; }
 inline u32 prefetch_l2(const void* p) { return *reinterpret_cast<const volatile u32*>(p); }
 inline void keep(u32) {}
 template <class T>

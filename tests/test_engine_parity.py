@@ -122,10 +122,8 @@ def test_engine_matches_golden_fixture(name):
     assert ee == g["errors"]
 
 
-@pytest.mark.parametrize("variant", ["5", "6"])
-def test_every_resolver_variant_is_exact(variant, monkeypatch):
-    """the round resolver and the block resolver must give identical placements."""
-    monkeypatch.setenv("SWP_RESOLVER", variant)
+def test_every_resolver_variant_is_exact():
+    """the block resolver must give the oracle's placements."""
     wl = synth.Workload("cfg4", T=4000, N=700)
     op, oe, _ = pu.oracle_run(wl)
     ep, ee, *_ = pu.engine_run(wl)

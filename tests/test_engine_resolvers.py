@@ -1,7 +1,7 @@
-"""GPU parity across the two resolver families and their geometries: 5, the round resolver (everything in one workgroup's LDS,
-the default where it fits), and 6, the block resolver (bitmap rows in global memory; beyond k_resolve5's node limit, for batches with
-more distinct reservations than k_resolve5 has rows for, for generic reservations) — at every owned-words-per-lane count K — must
-reproduce the oracle bit for bit. (The round-1 generations k_resolve / 1 / 2 / 3 and the scan they fed on were retired in round 3.)"""
+"""GPU parity of the block resolver (k_resolve6, bitmap rows in global memory) in its geometries: demand-class rows or rows per
+task of the block, with or without a compact index in front of every round, at every owned-words-per-lane count K — it must
+reproduce the oracle bit for bit. (The round-1 generations k_resolve / 1 / 2 / 3 and the scan they fed on were retired in round 3,
+the round resolver k_resolve5 after round 6: DESIGN.md §5a.)"""
 import os
 
 import pytest
@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture
 def resolver_env():
-    old = {k: os.environ.get(k) for k in ("SWP_RESOLVER", "SWP_R6_BLOCK", "SWP_R6_TASKROWS", "SWP_R6_COMPACT")}
+    old = {k: os.environ.get(k) for k in ("SWP_R6_BLOCK", "SWP_R6_TASKROWS", "SWP_R6_COMPACT")}
     yield
     for k, v in old.items():
         if v is None:
@@ -27,17 +27,13 @@ def pick_variant(variant):
     os.environ.pop("SWP_R6_TASKROWS", None)
     os.environ.pop("SWP_R6_COMPACT", None)
     if variant == "6c":   # the block resolver with a compact index in front of every round (k_r6_compact; by itself only after the symptom)
-        os.environ["SWP_RESOLVER"] = "6"
         os.environ["SWP_R6_COMPACT"] = "1"
     elif variant == "6t":   # the block resolver with ResourceFilter rows per task of the block instead of per demand class
-        os.environ["SWP_RESOLVER"] = "6"
         os.environ["SWP_R6_TASKROWS"] = "1"
-    else:
-        os.environ["SWP_RESOLVER"] = str(variant)
 
 
 CASES = [("cfg3", 2500, 300, {}), ("cfg4", 3000, 700, {}), ("cfg1", 500, 40, {}), ("cfg2", 3000, 50, {})]
-@pytest.mark.parametrize("variant", [5, 6, "6t", "6c"])
+@pytest.mark.parametrize("variant", [6, "6t", "6c"])
 @pytest.mark.parametrize("name,T,N,kw", CASES)
 def test_variants_agree_with_oracle(resolver_env, variant, name, T, N, kw):
     wl = synth.Workload(name, T=T, N=N, **kw)
@@ -57,7 +53,7 @@ def test_words_per_lane(N):
     pu.assert_same(op, oe, ep, ee)
 
 
-@pytest.mark.parametrize("variant", [5, 6, "6t", "6c"])
+@pytest.mark.parametrize("variant", [6, "6t", "6c"])
 @pytest.mark.parametrize("services,order", [(1, "rr"), (2, "rr"), (3, "major"), (40, "major"), (7, "rr")])
 def test_same_service_runs(resolver_env, variant, services, order):
     """Consecutive tasks of one service: every commit must be visible to the next task of that service although
@@ -69,10 +65,10 @@ def test_same_service_runs(resolver_env, variant, services, order):
     pu.assert_same(op, oe, ep, ee)
 
 
-def test_level_spread_beyond_the_round_resolvers_planes():
-    """One node keeps its count (it is DOWN) while the others take hundreds of tasks: the per-node spread outgrows the 255 levels
-    the round resolver keeps in LDS in the middle of a batch. The engine must carry on with the block resolver (16 planes in global
-    memory) from the task where the round resolver stopped — same placements as the oracle, no error."""
+def test_level_spread_of_500_levels():
+    """One node keeps its count (it is DOWN) while the others take hundreds of tasks: the per-node spread grows to 500 levels
+    over three ticks, beyond the 255 that 8 level planes hold. The block resolver (16 planes in global memory) must place every task
+    as the oracle does — same placements, no error."""
     import orc
     from swarmkit_amd import host as swhost
     o, e = orc.Oracle(), swhost.HostScheduler()

@@ -79,8 +79,7 @@ def test_sharded_equals_single_engine_at_scale(mode):
 
 @pytest.mark.parametrize("mode", MODES)
 def test_sharded_cfg4_200k_x_40k_equals_single_engine(mode):
-    """BASELINE configs[3] at a fifth of its size — past the node range of the round resolver, so the single engine runs the block
-    resolver — against 4 shards of 10k nodes. (The single-engine placement of exactly this case is pinned to the oracle's offline
+    """BASELINE configs[3] at a fifth of its size — the single engine runs the block resolver — against 4 shards of 10k nodes. (The single-engine placement of exactly this case is pinned to the oracle's offline
     digest by tests/test_engine_bigcases.py::cfg4_mid.)"""
     wl = synth.Workload("cfg4", T=200_000, N=40_000)
     ep, ee, *_ = pu.engine_run(wl)

@@ -45,7 +45,7 @@ def test_round_robin_order_has_no_runs_and_still_agrees(waterfill_env):
 
 @pytest.mark.parametrize("N", [1, 63, 65, 1025, 5000, 20000])
 def test_node_counts(waterfill_env, N):
-    """one node per thread, several per thread, fewer nodes than threads; beyond the round resolver's range too"""
+    """one node per thread, several per thread, fewer nodes than threads; up to 20 000 nodes"""
     wl = synth.Workload("cfg3", T=1500, N=N, services=4, order="major")
     run_both(wl, "1")
 

@@ -6,10 +6,10 @@ from collections import Counter
 
 d = '/tmp/swp_asm/'
 txt = open(d + 'resource_usage.txt').read()
-pat = sys.argv[1] if len(sys.argv) > 1 else 'resolve1'
+pat = sys.argv[1] if len(sys.argv) > 1 else 'k_explain'
 for b in re.split(r'Function Name: ', txt)[1:]:
     name = b.split()[0]
-    if pat not in name and 'r1_' not in name:
+    if pat not in name:
         continue
     def g(k):
         m = re.search(k + r': (\d+)', b)
@@ -17,7 +17,7 @@ for b in re.split(r'Function Name: ', txt)[1:]:
     print(name[:56].ljust(56), 'VGPR', g('VGPRs'), 'SGPR', g('TotalSGPRs'), 'scratch', g(r'ScratchSize \[bytes/lane\]'), 'occ', g(r'Occupancy \[waves/SIMD\]'),
           'spillV', g('VGPRs Spill'))
 s = open(d + 'swp_engine-hip-amdgcn-amd-amdhsa-gfx950.s').read()
-sym = sys.argv[2] if len(sys.argv) > 2 else '_ZN6swpdev10k_resolve1ILi3ELi8EEEvNS_11ResolveArgsE'
+sym = sys.argv[2] if len(sys.argv) > 2 else '_ZN6swpdev9k_explainENS_11ExplainArgsE'
 i = s.index(sym + ':')
 j = s.index('.end_amdhsa_kernel', i) if '.end_amdhsa_kernel' in s[i:] else len(s)
 lines = s[i:j].split('\n')

@@ -29,15 +29,12 @@ SCRATCH_OK = {
     "k_explain": "per-task Explain of tasks with generic reservations / mounts: small per-thread arrays",
     "k_vol_choose": "chooseTaskVolumes for one pair: per-mount arrays",
     "k_r6_volrows": "per-mount arrays",
-    "k_resolve5": "the round resolver (SWP_RESOLVER=5 only; behind the block resolver at every size since round 4): its listers' per-task arrays",
 }
 # 1024-thread kernels allowed above 120 VGPRs
 VGPR_EDGE_OK = {
     "k_groups2": "one workgroup per launch: the machine wave's three instances; no VGPR spills beyond the listed 4 is checked below",
-    "k_resolve5": "the round resolver (SWP_RESOLVER=5 only)",
 }
-VGPR_SPILL_OK = {"k_groups2": 12,    # (orderedNodes' second hand-out: swap-based moves of 16-byte records — rare paths; checked in the disassembly)
-                 "k_resolve5": 40}
+VGPR_SPILL_OK = {"k_groups2": 12}    # (orderedNodes' second hand-out: swap-based moves of 16-byte records — rare paths; checked in the disassembly)
 
 
 def demangle_short(name):

@@ -55,11 +55,6 @@ def draw(rng, which):
         s = rng.randrange(1, max(min(t, 300), 2))
         opts = "".join(o for o in "tc" if rng.random() < 0.3)
         return [seed, n, t, s, rng.choice([1, 32, 64, 128, 256, 512, 1024]), rng.randrange(3), rng.randrange(4), g] + ([opts] if opts else [])
-    if which == "resolve5":
-        n = pick_n(rng, rng.choice([1500, 13000]))
-        t = rng.randrange(1, 2200)
-        s = rng.randrange(1, max(min(t, 700), 2))
-        return [seed, n, t, s, rng.choice([7, 61, 300, 500, 512, 1000, 1024]), rng.randrange(3), rng.randrange(3)]
     if which == "scan":
         n = pick_n(rng, 4096)
         t = rng.randrange(1, 2000)
@@ -110,7 +105,7 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--sched", action="store_true", help="every run under its own random wave schedule (EMU_SCHED_SEED)")
     a = ap.parse_args()
-    bins = {"resolve6": build("emu_resolve6", "emu_resolve6.cpp"), "resolve7": build("emu_resolve7", "emu_resolve7.cpp"), "resolve5": build("emu_resolve5", "emu_resolve5.cpp"),
+    bins = {"resolve6": build("emu_resolve6", "emu_resolve6.cpp"), "resolve7": build("emu_resolve7", "emu_resolve7.cpp"),
             "scan": build("emu_scan", "emu_scan.cpp"), "groups": build("emu_groups", "emu_groups.cpp"), "groups_small": build("emu_groups_small", "emu_groups.cpp", ["-DG2_ARENA_LDS=3072"])}
     if a.only:
         bins = {k: v for k, v in bins.items() if k in a.only.split(",")}
@@ -122,8 +117,7 @@ def main():
         while time.time() < deadline or pending:
             while time.time() < deadline and len(pending) < a.jobs:
                 which = rng.choice(list(bins))
-                # (the round resolver answers "hundreds of levels" with ERR_LEVEL_RANGE and the engine goes on with the block resolver: not drawn for it)
-                lvl = rng.choice([4, 5]) if (which in ("resolve6", "resolve7", "scan") and rng.random() < 0.2) else (5 if which == "resolve5" and rng.random() < 0.1 else None)
+                lvl = rng.choice([4, 5]) if (which in ("resolve6", "resolve7", "scan") and rng.random() < 0.2) else None
                 pending.add(ex.submit(run, bins[which], draw(rng, which), rng.randrange(1, 1 << 30) if a.sched else 0, lvl))
             fin, pending = cf.wait(pending, return_when=cf.FIRST_COMPLETED)
             for f in fin:
