@@ -495,11 +495,29 @@ int swp_check_node(swp_engine*, const swp_task_desc* task, uint32_t node, int32_
  * ActiveTasksCountByService (unless SWP_TASK_UNCOUNTED), host ports, generic counts less the request — before the next pair of that
  * node is judged. first_fail[i] = -1 on pass, else the first failing filter 0..6 (as swp_check_node). Classes come from one pass
  * over the templates. Everything is validated first and the call is all or nothing: on any error nothing was applied. Refused
- * (SWP_EUNSUPPORTED): templates with cluster mounts (SWP_TASK_MOUNTS) — volume state is cluster-wide, such a task keeps swp_check_node
- * + swp_choose_volumes — and templates with spread preferences, which swp_check_node refuses too. */
+ * (SWP_EUNSUPPORTED): templates with cluster mounts (SWP_TASK_MOUNTS) — this entry has nowhere to report their attachments: such
+ * a list goes to swp_fit_pairs_volumes below — and templates with spread preferences, which swp_check_node refuses too. */
 typedef struct { uint32_t node; uint32_t tmpl; } swp_fit_pair;   /* 8 bytes */
 int swp_fit_pairs(swp_engine*, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs,
                   int32_t* first_fail);
+/* The same for a list in which templates may have cluster mounts, mixed freely with templates that have none. taskFitNode only CHOOSES
+ * volumes (chooseTaskVolumes reserves inside its loop and releases everything on return, volumes.go:98-134; checkVolume reads the tasks
+ * of a volume, volumes.go:257-316): the volume state is read-only for the whole pass, pairs on different nodes stay independent and the
+ * usage numbers (swp_volume_get_usage) are the same before and after the call. For a pair whose template has mounts:
+ *   - VolumesFilter (filter.go:424-432) is the pipeline's last entry: first_fail[i] = 7 when filters 0..6 pass and no mount has a volume
+ *     on the node;
+ *   - on a pass of all eight, chooseTaskVolumes on the node, every mount seeing the ones before it (as swp_choose_volumes). When every
+ *     mount finds a volume the pair passes (first_fail[i] = -1) and is booked on its node like any passing pair. When a mount finds none,
+ *     first_fail[i] = SWP_FIT_NO_VOLUME: the task is NOT assigned and NOT booked (scheduler.go:668-675), the next pair of the node sees
+ *     the node without it.
+ * out_att[i * SWP_MAX_MOUNTS + m] follows swp_batch_attachments' rows: the volume chosen for mount m of a passing pair; SWP_NO_VOLUME
+ * for every mount of a pair that failed a filter or has no mounts; for SWP_FIT_NO_VOLUME the prefix the mounts in front of the failing
+ * one chose, then SWP_NO_VOLUME — the failing mount is the first SWP_NO_VOLUME of the row, and the caller's volumeSet counts that
+ * prefix (volumes.go:104-131). Everything else as swp_fit_pairs: validated first, all or nothing, spread preferences refused, the node
+ * mirror folded; a call without any mount template returns swp_fit_pairs' verdicts and rows of SWP_NO_VOLUME. */
+#define SWP_FIT_NO_VOLUME 8   /* first_fail: all filters passed, chooseTaskVolumes found no volume for a mount (not a filter index) */
+int swp_fit_pairs_volumes(swp_engine*, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs,
+                          int32_t* first_fail, uint32_t* out_att /* [n_pairs][SWP_MAX_MOUNTS] */);
 
 /* constraintenforcer.rejectNoncompliantTasks (manager/orchestrator/constraintenforcer/constraint_enforcer.go:65-196)
  * over MANY nodes in one call: the enforcer's start-up sweep (Run, :45-52) or a burst of EventUpdateNode. Per node the

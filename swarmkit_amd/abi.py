@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SWP_LIB_PATH") or os.path.join(ROOT, "swarmkit_amd", 
 
 SWP_OK, SWP_EINVAL, SWP_ENOTFOUND, SWP_ENOMEM, SWP_EHIP, SWP_EUNSUPPORTED, SWP_ERANGE, SWP_ENODEVICE = 0, -1, -2, -3, -4, -5, -6, -7
 (SPACE_NODE_ID, SPACE_SERVICE, SPACE_LABEL_KEY, SPACE_FOLDED, SPACE_OS, SPACE_ARCH, SPACE_PLUGIN, SPACE_RAW, SPACE_GENERIC_KIND) = range(9)
+SPACE_VOLUME, SPACE_VOLUME_GROUP, SPACE_CSI = 9, 10, 11
 NODE_READY, NODE_HAS_DESC, NODE_HAS_PLATFORM, NODE_HAS_ENGINE = 0x1, 0x2, 0x4, 0x8
 NODE_HAS_LABELS, NODE_HAS_ELABELS, NODE_MANAGER, NODE_HAS_LOGPLUG, NODE_IP_VALID, NODE_IP_V4 = 0x10, 0x20, 0x40, 0x80, 0x100, 0x200
 (CK_NODE_ID, CK_HOSTNAME, CK_IP, CK_ROLE, CK_PLATFORM_OS, CK_PLATFORM_ARCH, CK_NODE_LABEL, CK_ENGINE_LABEL, CK_INVALID) = range(9)
@@ -109,7 +110,7 @@ EXPORTS = [
     "swp_create", "swp_destroy", "swp_reset", "swp_intern", "swp_intern_lookup", "swp_node_upsert", "swp_node_update_dynamic",
     "swp_node_remove", "swp_node_get", "swp_node_set_svc_count", "swp_node_get_svc_count", "swp_node_set_failures", "swp_node_port",
     "swp_constraint_set", "swp_platform_set", "swp_plugin_set", "swp_port_set", "swp_spread_set", "swp_schedule_groups", "swp_schedule_batch", "swp_batch_prepare",
-    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_enforce", "swp_node_matches",
+    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_node_matches",
     "swp_stats", "swp_strerror", "swp_last_error", "swp_abi_check", "swp_node_update_dynamic_many", "swp_node_get_many", "swp_shardset_create",
     "swp_shard_begin", "swp_shard_propose", "swp_shard_merge", "swp_shard_commit", "swp_shard_end", "swp_shard_run", "swp_rccl_available", "swp_rccl_unique_id", "swp_rccl_init", "swp_rccl_finalize", "swp_shard_run_rank", "swp_shard_verdict",
     # include/swp_sched.h — the host layer above the engine
@@ -119,7 +120,10 @@ EXPORTS = [
     "swp_constraint_parse", "swp_key_equal_fold", "swp_explain", "swp_parse_ip",
 ]
 # exports a library built against this header may lack (the host layer's CPU test double): the host layer declares them weak
-OPTIONAL = {"swp_fit_pairs"}
+OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes"}
+MAX_MOUNTS = 8              # SWP_MAX_MOUNTS
+NO_VOLUME = 0xFFFFFFFF      # SWP_NO_VOLUME
+FIT_NO_VOLUME = 8           # SWP_FIT_NO_VOLUME: swp_fit_pairs_volumes' first_fail for a failed chooseTaskVolumes
 
 
 class Unsupported(NotImplementedError):
@@ -212,6 +216,7 @@ def load_library(path=None):
         "swp_shard_run_rank": ([vp, vp, vp, u32, vp, vp], C.c_int),
         "swp_check_node": ([vp, P(TaskDesc), u32, P(i32)], C.c_int),
         "swp_fit_pairs": ([vp, vp, u32, vp, u32, vp], C.c_int),
+        "swp_fit_pairs_volumes": ([vp, vp, u32, vp, u32, vp, vp], C.c_int),
         "swp_enforce": ([vp, vp, u32, vp, u32, vp], C.c_int),
         "swp_node_matches": ([vp, vp, u32, vp, u32], C.c_int),
         "swp_stats": ([vp, P(Stats)], C.c_int),
@@ -608,6 +613,19 @@ class Engine:
         ff = np.empty(len(pairs), dtype=np.int32)
         self._ck(self.L.swp_fit_pairs(self.h, templates.ctypes.data, len(templates), pairs.ctypes.data, len(pairs), ff.ctypes.data))
         return ff
+
+    def fit_pairs_volumes(self, templates, pairs):
+        """swp_fit_pairs_volumes: fit_pairs for a list whose templates may have cluster mounts. Returns (first_fail, attachments):
+        first_fail as fit_pairs plus 7 (VolumesFilter) and FIT_NO_VOLUME (all filters passed, a mount found no volume: not applied);
+        attachments uint32 [pairs][MAX_MOUNTS], rows as batch_attachments' (NO_VOLUME where nothing was chosen)."""
+        templates = np.ascontiguousarray(templates, dtype=TASK_DTYPE)
+        if not isinstance(pairs, np.ndarray) or pairs.dtype != FIT_PAIR_DTYPE:
+            pairs = np.array([tuple(p) for p in pairs], dtype=FIT_PAIR_DTYPE)
+        pairs = np.ascontiguousarray(pairs)
+        ff = np.empty(len(pairs), dtype=np.int32)
+        att = np.full((len(pairs), MAX_MOUNTS), NO_VOLUME, dtype=np.uint32)
+        self._ck(self.L.swp_fit_pairs_volumes(self.h, templates.ctypes.data, len(templates), pairs.ctypes.data, len(pairs), ff.ctypes.data, att.ctypes.data))
+        return ff, att
 
     def stats(self):
         s = Stats()

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "swp_types.hpp"
+#include "swp_fitpairs.hpp"
 
 namespace swpdev {
 
@@ -850,34 +851,7 @@ __global__ void k_check_pair(CheckArgs a) {
 // two tasks): cpu / mem in registers, the generic counts, host-port claims and per-service counts in slots of its own. Different
 // nodes are independent. The thread is the only writer of its node, its slots and its pairs' verdicts: plain loads and stores.
 // ---------------------------------------------------------------------------------------------
-struct FitTmpl {
-    RTask rt;                 // the template's record (build_batch): classes, reservations, flags, MaxReplicas
-    u32 gen_off, n_gen;       // its generic reservations: gkind / gval[gen_off .. +n_gen)
-    u32 n_ports, pad;         // ports in its port set: a pair's port slots are port_slot[pair.port_off .. +n_ports)
-};
-static_assert(sizeof(FitTmpl) == 80, "FitTmpl layout");
-struct FitPair { u32 idx, tmpl, svc_slot, port_off; };   // idx: the pair's position in the caller's array
-struct FitArgs {
-    u32 n_seg, n_words, gstride, pad;
-    const u32* seg_node;      // [n_seg]
-    const u32* seg_off;       // [n_seg + 1] into pairs
-    const FitPair* pairs;
-    const FitTmpl* tm;
-    const u32* gkind;
-    const int32_t* gval;
-    const u32* port_slot;
-    u32* port_taken;          // per (segment, port): 1 = held on the node (its initial value: HostNode.ports)
-    u32* svc_cnt;             // per (segment, service): ActiveTasksCountByService (initial value: HostNode.svc)
-    const u64* ready;
-    const u64* con;
-    const u64* plat;
-    const u64* plug;
-    i64* cpu;
-    i64* mem;
-    u32* total;
-    int32_t* gcnt;            // [kind][gstride]
-    int32_t* out;             // first failing filter per pair, caller's order; -1 = passed (and applied)
-};
+// (FitTmpl, FitPair, FitArgs: swp_fitpairs.hpp, shared with the mount sibling k_fit_pairs_vol)
 __global__ __launch_bounds__(256) void k_fit_pairs(FitArgs a) {
     const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= a.n_seg) return;

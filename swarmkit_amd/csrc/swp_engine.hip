@@ -26,6 +26,7 @@
 
 #include "../../include/swp.h"
 #include "swp_device.hpp"
+#include "swp_fitpairs.hpp"
 #include "swp_groups.hpp"
 #include "swp_launch.hpp"
 #include "swp_resolve6.hpp"
@@ -2289,7 +2290,7 @@ int state_save(swp_engine*);
 int state_restore(swp_engine*);
 int commit(swp_engine*, const swp_placement*, uint32_t, int);
 int check_node(swp_engine*, const swp_task_desc*, uint32_t, int32_t*);
-int fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*);
+int fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*, uint32_t*);
 int enforce(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, uint8_t*);
 int node_matches(swp_engine*, const uint32_t*, uint32_t, uint64_t*, uint32_t);
 int stats(swp_engine*, swp_stats_t*);
@@ -4247,14 +4248,21 @@ int swp_check_node(swp_engine* e, const swp_task_desc* task, uint32_t node, int3
     return SWP_OK;
 }
 
-int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail) {
-    if (e && e->set) return ss::fit_pairs(e, templates, n_templates, pairs, n_pairs, first_fail);
-    if (!e || (!templates && n_templates) || (!pairs && n_pairs) || (!first_fail && n_pairs)) return SWP_EINVAL;
+// swp_fit_pairs (out_att == nullptr: templates with cluster mounts are refused) and swp_fit_pairs_volumes (out_att: [n_pairs][SWP_MAX_MOUNTS];
+// a call in which some template has mounts runs k_fit_pairs_vol, every other call the same k_fit_pairs)
+static_assert(FIT_FF_NO_VOLUME == SWP_FIT_NO_VOLUME && VOL_MAX_MOUNTS == SWP_MAX_MOUNTS, "the pair kernel reports in the C ABI's terms");
+static int fit_pairs_impl(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail,
+                          uint32_t* out_att) {
     if (n_pairs == 0) return SWP_OK;
     // everything is checked before the device is touched: a refused call leaves the mirror as it was
+    bool any_mounts = false;
     for (uint32_t t = 0; t < n_templates; ++t) {
         const swp_task_desc& d = templates[t];
-        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) {
+            if (!out_att) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+            if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) >= e->mount_sets.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown mount set", t);
+            any_mounts = true;
+        }
         if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
         if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
         if (d.service >= e->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
@@ -4307,6 +4315,7 @@ int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_temp
             }
         f.n_gen = (uint32_t)gkind.size() - f.gen_off;
         f.n_ports = templates[t].port_set ? (uint32_t)e->port_sets[templates[t].port_set].size() : 0u;
+        f.mset = templates[t].flags >> SWP_TASK_MOUNTS_SHIFT;
     }
     // per segment: a slot per service (its count on the node) and per host port (held or not) the segment's pairs name
     std::vector<uint32_t> seg_node(n_seg), seg_off(n_seg + 1), port_slot, port_taken, svc_cnt;
@@ -4357,7 +4366,7 @@ int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_temp
     const size_t o_node = place(seg_node.size() * 4), o_soff = place(seg_off.size() * 4), o_pair = place(fp.size() * sizeof(FitPair)),
                  o_tm = place(ft.size() * sizeof(FitTmpl)), o_gk = place(gkind.size() * 4), o_gv = place(gval.size() * 4),
                  o_ps = place(port_slot.size() * 4), o_pt = place(port_taken.size() * 4), o_sc = place(svc_cnt.size() * 4), up = off,
-                 o_out = place((size_t)n_pairs * 4);
+                 o_out = place((size_t)n_pairs * 4), o_att = any_mounts ? place((size_t)n_pairs * SWP_MAX_MOUNTS * 4) : 0;
     std::vector<unsigned char> blob(up);
     auto put = [&blob](size_t at, const void* src, size_t bytes) { if (bytes) std::memcpy(blob.data() + at, src, bytes); };
     put(o_node, seg_node.data(), seg_node.size() * 4);
@@ -4394,8 +4403,19 @@ int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_temp
     fa.total = e->d_total.as<uint32_t>();
     fa.gcnt = e->d_gcnt.as<int32_t>();
     fa.out = reinterpret_cast<int32_t*>(base + o_out);
-    hipLaunchKernelGGL(k_fit_pairs, dim3((n_seg + 255) / 256), dim3(256), 0, e->stream, fa);
-    HIPCHECK(e, hipGetLastError());
+    if (any_mounts) {   // VolumesFilter + chooseTaskVolumes per pair: the volume tables and topology bitmaps are current (flush_nodes above)
+        FitVolArgs va{};
+        va.f = fa;
+        if (!e->volumes.empty()) va.vol = vol_view(e);   // (no volume at all: n_vol == 0, every mount template fails VolumesFilter, as swp_check_node answers)
+        va.att = reinterpret_cast<u32*>(base + o_att);
+        hipError_t r = launch_fit_pairs_vol(va, e->stream);
+        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_fit_pairs_vol launch: %s", hipGetErrorString(r));
+        HIPCHECK(e, hipMemcpyAsync(out_att, base + o_att, (size_t)n_pairs * SWP_MAX_MOUNTS * 4, hipMemcpyDeviceToHost, e->stream));
+    } else {
+        hipLaunchKernelGGL(k_fit_pairs, dim3((n_seg + 255) / 256), dim3(256), 0, e->stream, fa);
+        HIPCHECK(e, hipGetLastError());
+        if (out_att) std::fill(out_att, out_att + (size_t)n_pairs * SWP_MAX_MOUNTS, SWP_NO_VOLUME);
+    }
     HIPCHECK(e, hipMemcpyAsync(first_fail, base + o_out, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHECK(e, hipStreamSynchronize(e->stream));
     // the passing pairs into the host mirror, as swp_batch_fetch folds a batch's placements (the device holds them already)
@@ -4413,6 +4433,19 @@ int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_temp
         host_apply_bulk(e, bulk, true, scr);
     }
     return SWP_OK;
+}
+
+int swp_fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail) {
+    if (e && e->set) return ss::fit_pairs(e, templates, n_templates, pairs, n_pairs, first_fail, nullptr);
+    if (!e || (!templates && n_templates) || (!pairs && n_pairs) || (!first_fail && n_pairs)) return SWP_EINVAL;
+    return fit_pairs_impl(e, templates, n_templates, pairs, n_pairs, first_fail, nullptr);
+}
+
+int swp_fit_pairs_volumes(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail,
+                          uint32_t* out_att) {
+    if (!e || (!templates && n_templates) || (!pairs && n_pairs) || ((!first_fail || !out_att) && n_pairs)) return SWP_EINVAL;
+    if (e->set) return ss::fit_pairs(e, templates, n_templates, pairs, n_pairs, first_fail, out_att);
+    return fit_pairs_impl(e, templates, n_templates, pairs, n_pairs, first_fail, out_att);
 }
 
 int swp_enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,

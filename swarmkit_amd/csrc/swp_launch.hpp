@@ -24,6 +24,8 @@ struct VolTopoArgs;
 struct VolChooseArgs;
 hipError_t launch_vol_topology(const VolTopoArgs& a, hipStream_t s);
 hipError_t launch_vol_choose(const VolChooseArgs& a, hipStream_t s);
+struct FitVolArgs;
+hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s);   // k_fit_pairs_vol (swp_fitpairs.hpp)
 
 // node-range shards, rounds on the device (swp_resolve7.hpp, built in swp_resolve6.hip)
 struct R7Args;

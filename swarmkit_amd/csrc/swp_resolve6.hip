@@ -9,6 +9,7 @@
 #define SWP_VOL_KERNELS
 #include "swp_resolve6.hpp"
 #include "swp_resolve7.hpp"
+#include "swp_fitpairs.hpp"
 #define SWP_SCAN_KERNELS
 #include "swp_scan.hpp"
 
@@ -68,6 +69,13 @@ hipError_t launch_vol_topology(const VolTopoArgs& a, hipStream_t s) {
 }
 hipError_t launch_vol_choose(const VolChooseArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_vol_choose, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// the preassigned pair pass of a call with cluster mounts (swp_fitpairs.hpp): one thread per node segment
+hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s) {
+    if (a.f.n_seg == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit_pairs_vol, dim3((a.f.n_seg + 255) / 256), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

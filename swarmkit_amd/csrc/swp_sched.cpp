@@ -38,6 +38,8 @@
 // Weak: an engine that does not export swp_fit_pairs (the CPU test double of tests/fake_swp.cpp) leaves it null, and
 // processPreassignedTasks then judges every task with swp_check_node, one call per task.
 extern "C" int swp_fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*) __attribute__((weak));
+// Weak as well: with it a task with cluster mounts joins the run; without it such a task keeps the per-task path and ends the run in front of it.
+extern "C" int swp_fit_pairs_volumes(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*, uint32_t*) __attribute__((weak));
 
 namespace swp {
 
@@ -1047,9 +1049,11 @@ class Scheduler {
     // processPreassignedTasks + taskFitNode, scheduler.go:398-426, 646-690. The pending tasks are walked in order; runs of them are
     // judged in ONE swp_fit_pairs call (the engine keeps the reference's per-node chain: a passing task is on its node before the next
     // task of that node is judged). A task the call cannot stand for goes through the per-task path below, behind the run before it:
-    // cluster mounts (volume state is cluster-wide), spread preferences (swp_check_node refuses them), a task already in its node's
-    // Tasks (addTask's state-change branches) and a generic kind its node lists irregularly (the engine's count -= request is not
-    // the reference's arithmetic there). Without swp_fit_pairs (an engine that does not export it) every task takes the per-task path.
+    // spread preferences (swp_check_node refuses them), a task already in its node's Tasks (addTask's state-change branches), a
+    // generic kind its node lists irregularly (the engine's count -= request is not the reference's arithmetic there) and — only
+    // when the engine lacks swp_fit_pairs_volumes — cluster mounts. With that entry a mount task joins the run: taskFitNode only
+    // chooses volumes (scheduler.go:663-677), so the volume state is read-only for the pass and a run that holds a mount template
+    // is one swp_fit_pairs_volumes call. Without swp_fit_pairs (an engine that does not export it) every task takes the per-task path.
     struct PreItem {
         std::string tid;
         Value t;
@@ -1085,8 +1089,8 @@ class Scheduler {
                 run.push_back(PreItem{tid, t, &n->second, NO_TMPL, deferredWhy(f)});
                 continue;
             }
-            if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) || d.spread_set || !clusterMounts(t).empty() || n->second.Tasks.find(tid) != nullptr ||
-                reservesIrregular(t, n->second)) {
+            const bool mounts_alone = swp_fit_pairs_volumes == nullptr && ((d.flags >> SWP_TASK_MOUNTS_SHIFT) || !clusterMounts(t).empty());
+            if (mounts_alone || d.spread_set || n->second.Tasks.find(tid) != nullptr || reservesIrregular(t, n->second)) {
                 flush();
                 preassignedOne(tid, t, n->second, decisions, &d);
                 continue;
@@ -1116,7 +1120,9 @@ class Scheduler {
     }
     // one swp_fit_pairs call for a run, then the decisions in the run's order; the engine applied the passing tasks already, what is
     // left is the host half of addTask (nodeinfo.go:128-137: Claim, Tasks). A refused call applied nothing: the run goes through the
-    // per-task path, which reproduces its Deferred lines.
+    // per-task path, which reproduces its Deferred lines. A run that holds a template with cluster mounts goes through
+    // swp_fit_pairs_volumes: a passing mount task carries its attachments (chooseForPreassigned's document), one whose choice failed
+    // keeps its state with the reference's error; either way the volumeSet counts what the temporary reservations leave behind.
     void flushPreassigned(const std::vector<PreItem>& run, const std::vector<swp_task_desc>& tmpls, Decisions& decisions) {
         if (run.empty()) return;
         std::vector<swp_fit_pair> pairs;
@@ -1124,7 +1130,13 @@ class Scheduler {
         for (const PreItem& it : run)
             if (it.tmpl != NO_TMPL) pairs.push_back(swp_fit_pair{it.ni->idx, it.tmpl});
         std::vector<int32_t> ff(pairs.size(), -1);
-        if (!pairs.empty() && swp_fit_pairs(e_, tmpls.data(), (uint32_t)tmpls.size(), pairs.data(), (uint32_t)pairs.size(), ff.data()) != SWP_OK) {
+        std::vector<uint32_t> att;
+        bool with_mounts = false;
+        for (const swp_task_desc& d : tmpls) with_mounts = with_mounts || (d.flags >> SWP_TASK_MOUNTS_SHIFT) != 0;
+        if (with_mounts) att.assign(pairs.size() * (size_t)SWP_MAX_MOUNTS, SWP_NO_VOLUME);
+        if (!pairs.empty() &&
+            (with_mounts ? swp_fit_pairs_volumes(e_, tmpls.data(), (uint32_t)tmpls.size(), pairs.data(), (uint32_t)pairs.size(), ff.data(), att.data())
+                         : swp_fit_pairs(e_, tmpls.data(), (uint32_t)tmpls.size(), pairs.data(), (uint32_t)pairs.size(), ff.data())) != SWP_OK) {
             for (const PreItem& it : run) preassignedOne(it.tid, it.t, *it.ni, decisions);
             return;
         }
@@ -1137,9 +1149,20 @@ class Scheduler {
                 decisions.end();
                 continue;
             }
+            const uint32_t* row = with_mounts ? &att[k * (size_t)SWP_MAX_MOUNTS] : nullptr;
             const int32_t f = ff[k++];
             Value newT = it.t.shallow_copy();
-            if (f >= 0) {
+            const bool has_mounts = (tmpls[it.tmpl].flags >> SWP_TASK_MOUNTS_SHIFT) != 0;
+            if (f == SWP_FIT_NO_VOLUME) {   // scheduler.go:663-674: every filter passed, a mount found no volume — not assigned, not on its node
+                const std::vector<const Value*> cms = clusterMounts(it.t);
+                size_t failed = 0;
+                while (failed < cms.size() && failed < SWP_MAX_MOUNTS && row[failed] != SWP_NO_VOLUME) ++failed;
+                bookChooseRemainder(row, std::min(failed, cms.size()), as_str(it.ni->node.get("ID")));
+                Value status = statusCopy(it.t);
+                status.set("Err", Value::str("cannot find volume to satisfy mount with source " + as_str(cms[std::min(failed, cms.size() - 1)]->get("Source"))));
+                newT.set("Status", status);
+                allTasks_[it.tid] = newT;
+            } else if (f >= 0) {
                 uint32_t hist[SWP_NFILTERS] = {0};
                 hist[f] = 1;
                 Value status = statusCopy(it.t);
@@ -1147,6 +1170,20 @@ class Scheduler {
                 newT.set("Status", status);
                 allTasks_[it.tid] = newT;
             } else {
+                if (has_mounts) {   // the attachments first, as chooseForPreassigned leaves the document
+                    const std::vector<const Value*> cms = clusterMounts(it.t);
+                    bookChooseRemainder(row, cms.size(), as_str(it.ni->node.get("ID")));
+                    Value vols = Value::array();
+                    for (size_t m = 0; m < cms.size(); ++m) {
+                        if (row[m] >= vol_idx_to_id_.size()) fail(SWP_EINVAL, "engine returned an unknown volume index");
+                        Value va = Value::object();
+                        va.set("ID", Value::str(vol_idx_to_id_[row[m]]));
+                        va.set("Source", Value::str(as_str(cms[m]->get("Source"))));
+                        va.set("Target", Value::str(as_str(cms[m]->get("Target"))));
+                        vols.push(va);
+                    }
+                    newT.set("Volumes", vols);
+                }
                 Value status = Value::object();
                 status.set("State", Value::integer(ASSIGNED));
                 status.set("Message", Value::str("scheduler confirmed task can run on preassigned node"));

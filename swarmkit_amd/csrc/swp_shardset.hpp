@@ -604,8 +604,11 @@ int check_node(swp_engine* e, const swp_task_desc* task, uint32_t node, int32_t*
 
 // swp_fit_pairs: every pair goes to the owner of its node (a node never spans shards, so each shard's chain is the whole chain of its
 // nodes), the sub-lists keep the caller's order. All or nothing across the set: everything every shard would refuse is refused here
-// before the first shard runs; what is left to fail after that is the device itself.
-int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail) {
+// before the first shard runs; what is left to fail after that is the device itself. out_att (swp_fit_pairs_volumes; nullptr: swp_fit_pairs,
+// mount templates refused): the volume table is replicated and the pass reserves nothing, so every shard judges its pairs against the same
+// volumes; a single-node volume in use on another shard's node carries a foreign pin there (volume_set_usage above), which equals none
+// of the shard's own nodes — what swp_check_node / swp_choose_volumes see through the same owner routing.
+int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_templates, const swp_fit_pair* pairs, uint32_t n_pairs, int32_t* first_fail, uint32_t* out_att) {
     ShardSet& S = *e->set;
     if ((!templates && n_templates) || (!pairs && n_pairs) || (!first_fail && n_pairs)) return SWP_EINVAL;
     if (S.broken) return broken_error(e);
@@ -613,7 +616,8 @@ int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_template
     const swp_engine* c0 = S.sh[0];   // (predicate sets and ids are replicated: shard 0 speaks for all)
     for (uint32_t t = 0; t < n_templates; ++t) {
         const swp_task_desc& d = templates[t];
-        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+        if (!out_att && (d.flags >> SWP_TASK_MOUNTS_SHIFT)) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+        if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) >= c0->mount_sets.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown mount set", t);
         if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
         if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
         if (d.service >= c0->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
@@ -632,11 +636,18 @@ int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_template
         src[g].push_back(i);
     }
     std::vector<int32_t> ff;
+    std::vector<uint32_t> att;
     for (size_t g = 0; g < per.size(); ++g) {
         if (per[g].empty()) continue;
         ff.resize(per[g].size());
-        if (int rc = swp_fit_pairs(S.sh[g], templates, n_templates, per[g].data(), (uint32_t)per[g].size(), ff.data())) return take_error(e, S.sh[g], rc);
-        for (size_t k = 0; k < ff.size(); ++k) first_fail[src[g][k]] = ff[k];
+        if (out_att) att.resize(per[g].size() * (size_t)SWP_MAX_MOUNTS);
+        const int rc = out_att ? swp_fit_pairs_volumes(S.sh[g], templates, n_templates, per[g].data(), (uint32_t)per[g].size(), ff.data(), att.data())
+                               : swp_fit_pairs(S.sh[g], templates, n_templates, per[g].data(), (uint32_t)per[g].size(), ff.data());
+        if (rc) return take_error(e, S.sh[g], rc);
+        for (size_t k = 0; k < ff.size(); ++k) {
+            first_fail[src[g][k]] = ff[k];
+            if (out_att) std::memcpy(out_att + (size_t)src[g][k] * SWP_MAX_MOUNTS, att.data() + k * SWP_MAX_MOUNTS, SWP_MAX_MOUNTS * 4);
+        }
     }
     return SWP_OK;
 }

@@ -9,11 +9,16 @@
   loop_ms             ... against swp_check_node + swp_commit per pair on a twin engine (measured over the first --loop-pairs pairs,
                       scaled to all of them: loop_us_per_pair)
 
+--mounts all|alternate gives the services' tasks one cluster mount on a `group:` volume (every service; every second one) and orders the
+pending list node by node, so that mount tasks and plain tasks alternate in it: an engine without swp_fit_pairs_volumes ends a run at every
+mount task. The engine call is then swp_fit_pairs_volumes and the loop adds swp_choose_volumes.
+
 --lib PATH runs the host-layer figures against another build of libswp.so (an older commit's, for a same-box "before"); a library
 without swp_fit_pairs takes the per-task path and the engine-call figures are left out.
 
-usage: python tools/bench_preassigned.py [--nodes 10000] [--services 1 4] [--reps 3] [--lib PATH]"""
+usage: python tools/bench_preassigned.py [--nodes 10000] [--services 1 4] [--reps 3] [--mounts none|all|alternate] [--lib PATH]"""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -26,26 +31,38 @@ sys.path.insert(0, ROOT)
 from swarmkit_amd import abi, sched as swsched  # noqa: E402
 
 RUNNING, PENDING, READY = 512, 64, 2
+MOUNTS = "none"   # --mounts
+
+
+def mounts_of(k):
+    return MOUNTS == "all" or (MOUNTS == "alternate" and k % 2 == 1)
 
 
 def node_doc(i, small):
     return {"ID": "n%06d" % i, "Spec": {"Annotations": {"Name": "node%d" % i, "Labels": {"zone": "z%d" % (i % 4)}}, "Availability": 0},
             "Status": {"State": READY, "Addr": "10.%d.%d.%d" % (i >> 16, (i >> 8) & 255, i & 255)},
             "Description": {"Hostname": "h%d" % i, "Platform": {"Architecture": "amd64", "OS": "linux"},
-                            "Resources": {"NanoCPUs": 10**8 if small else 64 * 10**9, "MemoryBytes": 256 << 30}}}
+                            "Resources": {"NanoCPUs": 10**8 if small else 64 * 10**9, "MemoryBytes": 256 << 30},
+                            **({} if MOUNTS == "none" else {"CSIInfo": [{"PluginName": "csi-a", "NodeID": "c%d" % i}]})}}
 
 
 def task_doc(k, i):
-    return {"ID": "g%02d-%06d" % (k, i), "ServiceID": "gsvc%02d" % k, "NodeID": "n%06d" % i, "DesiredState": RUNNING,
-            "Status": {"State": PENDING},
-            "Spec": {"Resources": {"Reservations": {"NanoCPUs": 10**9 // 4, "MemoryBytes": 1 << 28}},
-                     "Placement": {"Constraints": ["node.labels.zone!=nowhere"], "Platforms": [{"Architecture": "amd64", "OS": "linux"}]}}}
+    spec = {"Resources": {"Reservations": {"NanoCPUs": 10**9 // 4, "MemoryBytes": 1 << 28}},
+            "Placement": {"Constraints": ["node.labels.zone!=nowhere"], "Platforms": [{"Architecture": "amd64", "OS": "linux"}]}}
+    if mounts_of(k):
+        spec["Container"] = {"Mounts": [{"Type": "CLUSTER", "Source": "group:g", "Target": "/data"}]}
+    tid = "g%02d-%06d" % (k, i) if MOUNTS == "none" else "t%06d-%02d" % (i, k)   # (pending tasks are walked in ascending ID)
+    return {"ID": tid, "ServiceID": "gsvc%02d" % k, "NodeID": "n%06d" % i, "DesiredState": RUNNING, "Status": {"State": PENDING}, "Spec": spec}
 
 
 def scheduler(lib, N, S, small_every=0):
     s = swsched.Scheduler(engine=abi.Engine(lib_path=lib))
     for i in range(N):
         s.create_node(node_doc(i, small_every and i % small_every == 0))
+    if MOUNTS != "none":
+        s.update_volume({"ID": "v0", "Spec": {"Annotations": {"Name": "vol0"}, "Group": "g", "Driver": {"Name": "csi-a"},
+                                              "AccessMode": {"Scope": "MULTI_NODE", "Sharing": "ALL"}, "Availability": "ACTIVE"},
+                         "VolumeInfo": {"VolumeID": "plug0", "AccessibleTopology": []}})
     for k in range(S):
         s.set_service("gsvc%02d" % k)
         for i in range(N):
@@ -71,10 +88,15 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--lib", default=None)
     ap.add_argument("--loop-pairs", type=int, default=2000)
+    ap.add_argument("--mounts", choices=["none", "all", "alternate"], default="none")
     a = ap.parse_args()
+    global MOUNTS
+    MOUNTS = a.mounts
     lib = a.lib or abi.build_library()
-    has_fit = hasattr(abi.load_library(lib), "swp_fit_pairs")
-    out = {"tool": "bench_preassigned", "nodes": a.nodes, "lib": os.path.relpath(lib, ROOT) if a.lib else "tree", "fit_pairs_exported": has_fit, "cases": []}
+    L = abi.load_library(lib)
+    has_fit = hasattr(L, "swp_fit_pairs") and (MOUNTS == "none" or hasattr(L, "swp_fit_pairs_volumes"))
+    out = {"tool": "bench_preassigned", "nodes": a.nodes, "mounts": MOUNTS, "lib": os.path.relpath(lib, ROOT) if a.lib else "tree", "fit_pairs_exported": hasattr(L, "swp_fit_pairs"),
+           "fit_pairs_volumes_exported": hasattr(L, "swp_fit_pairs_volumes"), "cases": []}
     for S in a.services:
         c = {"services": S, "tasks": a.nodes * S}
         best = {}
@@ -103,17 +125,25 @@ def main():
             fa.e.state_save()
             times = []
             for _ in range(a.reps + 1):
-                ms, ff = timed(lambda: fa.e.fit_pairs(tmpls, pairs))
+                if MOUNTS == "none":
+                    ms, ff = timed(lambda: fa.e.fit_pairs(tmpls, pairs))
+                else:
+                    ms, (ff, att) = timed(lambda: fa.e.fit_pairs_volumes(tmpls, pairs))
+                    assert ((att[:, 0] != abi.NO_VOLUME) == np.array([mounts_of(int(k)) for k in pairs["tmpl"]])).all()
                 times.append(ms)
                 assert (ff == -1).all()
                 fa.e.state_restore()
             c["fit_pairs_ms"] = round(min(times[1:]), 3)   # (the first call warms the arena and the module)
             n = min(a.loop_pairs, len(pairs))
+            fb.e.L.swp_choose_volumes.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            row, n_out, failed = (ctypes.c_uint32 * abi.MAX_MOUNTS)(), ctypes.c_uint32(), ctypes.c_uint32()
 
             def loop():
                 for node, k in pairs[:n]:
                     t = tmplb[k]
                     if fb.e.check_node(t, int(node)) == -1:
+                        if int(t["flags"]) >> 8:
+                            fb.e._ck(fb.e.L.swp_choose_volumes(fb.e.h, int(t["flags"]) >> 8, int(node), row, ctypes.byref(n_out), ctypes.byref(failed)))
                         fb.e.commit(np.array([(node, t["service"], t["cpu"], t["mem"], t["port_set"], 1)], dtype=abi.PLACEMENT_DTYPE))
             ms, _ = timed(loop)
             c["loop_pairs_timed"] = n
