@@ -3,7 +3,12 @@
 // with the sequential model of emu_model.hpp; the bitmaps the kernels maintain incrementally (level planes, demand-class
 // rows) are compared with a rebuild from the final node rows. TEST INFRASTRUCTURE (tests/test_emu_resolve6.py); not product.
 //
-//   emu_resolve6 <seed> <N> <T> <S> <block> <order: 0 rr | 1 major | 2 random> <features 0..3> [v] [s: two stretches with a rebuild between]
+//   emu_resolve6 <seed> <N> <T> <S> <block> <order: 0 rr | 1 major | 2 random> <features 0..4> [v] [s: two stretches with a rebuild between]
+// Feature level 4: level 3 + tasks with cluster mounts (CSI volumes, swp_volumes.hpp): k_r6_volrows in front of each round, k_r6_commit_v
+// instead of k_r6_commit, as swp_resolve6.hip launches them; the model places such a task on the first candidate that also passes its
+// VolumesFilter as the volumes stand at that moment, chooses and reserves. Compared in addition: the attachment rows and every volume's
+// final usage. m<k>: one task in k has mounts (default 10); a: tasks 0 and 1 both have; h: half of them want ONE single-node volume;
+// w: half of them want to write to ONE multi-node volume for one writer (a second one in the same block would be decided on a stale row).
 #include "wv_emu.hpp"
 
 #define SWP_R6_KERNELS
@@ -26,7 +31,8 @@ int main(int argc, char** argv) {
     if (argc < 8) { fprintf(stderr, "usage: %s seed N T S block order features(0..3) [v] [s]\n", argv[0]); return 2; }
     const u32 seed = atoi(argv[1]), N = atoi(argv[2]), T = atoi(argv[3]), S = atoi(argv[4]), B = atoi(argv[5]);
     const int order = atoi(argv[6]), feat = atoi(argv[7]);
-    bool verbose = false, split = false, task_rows = false, twins = true, compact = false, fused = false;
+    bool verbose = false, split = false, task_rows = false, twins = true, compact = false, fused = false, adjacent = false, hot = false, writer = false;
+    u32 every = 10;
     for (int i = 8; i < argc; ++i) {
         if (argv[i][0] == 'v') verbose = true;
         if (argv[i][0] == 's') split = true;
@@ -34,8 +40,22 @@ int main(int argc, char** argv) {
         if (argv[i][0] == 'c') compact = true;     // a compact index of the lowest level's nodes in front of every round (k_r6_compact)
         if (argv[i][0] == 'f') compact = fused = true;   // ... built at the END of k_r6_commit_c for the next round (R6Args.compact == 2); k_r6_compact itself only in front of every fifth round (a chunk's first)
         if (argv[i][0] == 'n') twins = false;      // lists start at the level's first candidate (R6Args.tmpl == nullptr: what the shard drivers run)
+        if (argv[i][0] == 'm') every = std::max(atoi(argv[i] + 1), 1);
+        if (argv[i][0] == 'a') adjacent = true;
+        if (argv[i][0] == 'h') hot = true;
+        if (argv[i][0] == 'w') writer = true;
     }
+    const bool mounts = feat >= 4;
+    if (mounts && compact) { fprintf(stderr, "a batch with cluster mounts runs without the compact index (launch_r6_rounds)\n"); return 2; }
     Problem p = make_problem(seed, N, T, S, order, feat);
+    VolProblem vp;
+    MountRun mr;
+    VolTables vt;
+    if (mounts) {
+        vp = make_volumes(seed, N, 8, 30, hot ? 6 : 0);
+        mr = make_mounts(vp, seed, T, every, adjacent, hot ? 6 : 0, false, writer);
+        vt = vol_tables(vp);
+    }
     // demand classes over the raw reservations (what the engine's batch preparation does)
     std::set<i64> sc, sm;
     for (const RTask& r : p.rt)
@@ -54,7 +74,7 @@ int main(int argc, char** argv) {
     State ref = initial_state(p), em = initial_state(p);
     std::vector<u64> F;
     scan_window(p, ref, 0, T, F);
-    ref_window(p, ref, 0, T, F);
+    ref_window(p, ref, 0, T, F, mounts ? &mr : nullptr);
 
     std::vector<u64> planes((size_t)R6_NP * p.Wn, 0xAAAAAAAAAAAAAAAAull), rr((size_t)std::max<u32>(n_dc + n_dm, 1) * p.Wn, 0x5555555555555555ull);
     std::vector<R6Prop> prop(B);
@@ -111,14 +131,25 @@ int main(int argc, char** argv) {
         a.rg_k1 = p.rg_k1.data();
     }
 
+    std::vector<u64> vrows(std::max<size_t>(mr.csi_set.size(), 1) * p.Wn, 0x9999999999999999ull);
+    std::vector<u32> att(std::max<size_t>(mr.csi_set.size(), 1) * VOL_MAX_MOUNTS, VOL_NONE);
+    if (mounts) {
+        a.csi_of = mr.csi_of.data();
+        a.csi_set = mr.csi_set.data();
+        a.vrows = vrows.data();
+        a.att = att.data();
+        a.vol = vt.view();
+    }
+    u64 cut_at_mount = 0;   // rounds that ended early, in front of a task with mounts, having decided one
+
     // identical tasks: the first task with the same record (but for its list slot) and generic set — what the engine's batch preparation
     // derives from the descriptors
     std::vector<u32> tmpl(T);
     {
-        std::map<std::tuple<u32, u32, u32, i64, i64, u32, u64, u32>, u32> first;
+        std::map<std::tuple<u32, u32, u32, i64, i64, u32, u64, u32, u32>, u32> first;
         for (u32 j = 0; j < T; ++j) {
             const RTask& r = p.rt[j];
-            tmpl[j] = first.emplace(std::make_tuple(r.svc, r.sc, r.flags, r.cpu, r.mem, r.pset, r.maxrep, p.tg.empty() ? 0u : p.tg[j]), j).first->second;
+            tmpl[j] = first.emplace(std::make_tuple(r.svc, r.sc, r.flags, r.cpu, r.mem, r.pset, r.maxrep, p.tg.empty() ? 0u : p.tg[j], mounts && mr.is(j) ? mr.csi_set[mr.csi_of[j]] : 0u), j).first->second;
         }
     }
     a.tmpl = twins ? tmpl.data() : nullptr;
@@ -165,6 +196,17 @@ int main(int argc, char** argv) {
                 if (on) ++crounds_checked;
                 grid(B, 64 * R6_PW, r6_propose_lds(p.Wn), [a]() { k_r6_propose_c(a); });
                 grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm, true), [a]() { k_r6_commit_c(a); });
+            } else if (mounts) {
+                for (u32 by = 0; by < B; ++by) {   // grid (words / 256, block)
+                    emu::blockidx_y() = by;
+                    grid((p.Wn + 255) / 256, 256, 0, [a]() { k_r6_volrows(a); });
+                }
+                emu::blockidx_y() = 0;
+                grid(B, 64 * R6_PW, r6_propose_lds(p.Wn), [a]() { k_r6_propose(a); });
+                grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm), [a]() { k_r6_commit_v(a); });
+                if (blk.pos < std::min(before + B, blk.end) && mr.is(blk.pos))
+                    for (u32 j = before; j < blk.pos; ++j)
+                        if (mr.is(j)) { ++cut_at_mount; break; }
             } else {
                 grid(B, 64 * R6_PW, r6_propose_lds(p.Wn), [a]() { k_r6_propose(a); });
                 grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm), [a]() { k_r6_commit(a); });
@@ -180,7 +222,8 @@ int main(int argc, char** argv) {
             grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm, true), [a]() { k_r6_commit_c(a); });
         } else {
             grid(B, 64 * R6_PW, r6_propose_lds(p.Wn), [a]() { k_r6_propose(a); });
-            grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm), [a]() { k_r6_commit(a); });
+            if (mounts) grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm), [a]() { k_r6_commit_v(a); });
+            else grid(1, R6_COMMIT_THREADS, r6_commit_lds(p.Wn, B, n_dc + n_dm), [a]() { k_r6_commit(a); });
         }
         return blk.pos == j1;
     };
@@ -196,6 +239,22 @@ int main(int argc, char** argv) {
     ok = ok && same("log_node", em.log_node, ref.log_node, ref.ctl.ncommit) && same("log_task", em.log_task, ref.log_task, ref.ctl.ncommit) &&
          same("log_prev", em.log_prev, ref.log_prev, ref.ctl.ncommit) && same("last", em.last, ref.last, N) &&
          same("inf_task", em.inf_task, ref.inf_task, ref.ctl.ninf) && same("inf_pos", em.inf_pos, ref.inf_pos, ref.ctl.ninf);
+    if (mounts) {   // the attachment rows of every task with mounts, the final usage of every volume
+        ok = ok && same("att", att, mr.att, mr.csi_set.size() * VOL_MAX_MOUNTS);
+        for (u32 v = 0; ok && v < vp.vol.size(); ++v) {
+            const VolDyn want = vp.derive(mr.use, v), d = vt.vdyn[v];
+            if (d.n_tasks != want.n_tasks || d.n_writers != want.n_writers || (want.n_tasks && d.pin != want.pin)) {
+                fprintf(stderr, "MISMATCH usage of volume %u: emu {%u tasks, %u writers, pin %08x} model {%u, %u, %08x}\n", v, d.n_tasks, d.n_writers, d.pin, want.n_tasks, want.n_writers, want.pin);
+                ok = false;
+            }
+        }
+        u64 pin_on = 0, pin_failed = 0, pin_elsewhere = 0;   // the tasks after the pinned single-node volume: on its node, or nowhere
+        for (u32 j = 0; hot && j < T; ++j)
+            if (mr.is(j) && mr.csi_set[mr.csi_of[j]] <= 6) (ref.out[j] == (int32_t)N - 1 ? pin_on : ref.out[j] < 0 ? pin_failed : pin_elsewhere)++;
+        fprintf(stderr, "reach mounts: tasks=%zu with_attachments=%llu failed_choice=%llu no_node=%llu cut_at_second_mount=%llu pinned_on_node=%llu pinned_unplaced=%llu pinned_elsewhere=%llu\n",
+                mr.csi_set.size(), (unsigned long long)mr.with_att, (unsigned long long)mr.failed_choice, (unsigned long long)mr.no_node, (unsigned long long)cut_at_mount,
+                (unsigned long long)pin_on, (unsigned long long)pin_failed, (unsigned long long)pin_elsewhere);
+    }
     // the incrementally maintained bitmaps against a rebuild from the final node rows (same base: levels are relative to it)
     if (ok) {
         std::vector<u64> planes2 = planes, rr2 = rr, rg2 = rg;

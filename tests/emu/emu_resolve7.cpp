@@ -4,7 +4,12 @@
 // with the sequential model of emu_model.hpp run over the WHOLE node set. What a job of G GPUs computes, without a GPU.
 // TEST INFRASTRUCTURE (tests/test_emu_resolve7.py); not product.
 //
-//   emu_resolve7 <seed> <N> <T> <S> <block> <order: 0 rr | 1 major | 2 random> <features 0..3> <shards> [v] [t: task rows] [r<rank>]
+//   emu_resolve7 <seed> <N> <T> <S> <block> <order: 0 rr | 1 major | 2 random> <features 0..4> <shards> [v] [t: task rows] [r<rank>]
+// Feature level 4 (not in the rank variant): level 3 + tasks with cluster mounts. Every shard holds its own replica of the volume table (T rows
+// of its range, a pin as its local node on the owner and as the foreign code elsewhere), k_r7_volrows in front of the proposals,
+// k_r7_commit_v, the trailer slots behind the proposals as swp_shardset wires them, k_r7_settle behind the last round. Compared in
+// addition: every attachment row (on the owner; VOL_NONE elsewhere) and EVERY shard's final usage numbers against the model's derived
+// ones. m<k>: one task in k has mounts; a: tasks 0 and 1 both have; l: the batch's last task has; e<g>: range g is empty of valid nodes.
 // r<rank>: the RANK variant (swp_shard_run_rank's protocol): this process runs the kernels of ONE shard only; per round it writes its
 // block of R6Prop records to stdout (a u32 1 in front; a u32 0 when the batch is done), reads the blocks of ALL ranks back from stdin
 // in rank order — the layout ncclAllGather leaves in d_all — folds + matches them itself and applies the picks of its own range.
@@ -97,6 +102,9 @@ struct Shard {
     std::vector<R6Prop> prop;   // [B] + the tail (trailer slots, dead word): what a shard contributes to a round's exchange
     Blk6 blk{};
     u32 first = 0;
+    VolTables vt;               // feature level 4: this shard's replica of the volume table
+    std::vector<u64> vrows;
+    std::vector<u32> att;
 };
 
 // The cluster after a batch, as the NEXT batch finds it (the incremental path between two batches: scheduler.go:254-396, nodeinfo.go:66-154):
@@ -172,26 +180,45 @@ static Problem next_problem(const Problem& p, const State& fin) {
     return q;
 }
 
-static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int feat, u32 G, bool verbose, bool task_rows, int my_rank);
+struct MountOpts { u32 every = 10; bool adjacent = false, last = false; };
+static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int feat, u32 G, bool verbose, bool task_rows, int my_rank, const MountOpts* mo = nullptr);
 
 int main(int argc, char** argv) {
     if (argc < 9) { fprintf(stderr, "usage: %s seed N T S block order features(0..3) shards [v] [t] [r<rank>] [c: a second batch after node and task events]\n", argv[0]); return 2; }
     const u32 seed = atoi(argv[1]), N = atoi(argv[2]), T = atoi(argv[3]), S = atoi(argv[4]), B = atoi(argv[5]);
-    const int order = atoi(argv[6]), feat = std::min(atoi(argv[7]), 3);
+    const int order = atoi(argv[6]), feat = std::min(atoi(argv[7]), 4);
     const u32 G = atoi(argv[8]);
     bool verbose = false, task_rows = false, churn = false;
+    MountOpts mo;
+    int empty_range = -1;
     int my_rank = -1;   // >= 0: the rank variant
     for (int i = 9; i < argc; ++i) {
         if (argv[i][0] == 'v') verbose = true;
         if (argv[i][0] == 't') task_rows = true;
         if (argv[i][0] == 'r') my_rank = atoi(argv[i] + 1);
         if (argv[i][0] == 'c') churn = true;
+        if (argv[i][0] == 'm') mo.every = std::max(atoi(argv[i] + 1), 1);
+        if (argv[i][0] == 'a') mo.adjacent = true;
+        if (argv[i][0] == 'l') mo.last = true;
+        if (argv[i][0] == 'e') empty_range = atoi(argv[i] + 1);
     }
+    if (feat >= 4 && (my_rank >= 0 || churn)) { fprintf(stderr, "feature level 4 runs one batch over a shard set\n"); return 2; }
     if (my_rank >= (int)atoi(argv[8])) { fprintf(stderr, "rank %d of %s shards\n", my_rank, argv[8]); return 2; }
     if (G < 1 || G > R7_MAXS || G > N) { fprintf(stderr, "1..%d shards, at most one per node\n", R7_MAXS); return 2; }
     Problem p = make_problem(seed, N, T, S, order, feat);
+    if (empty_range >= 0) {   // a range without a valid node: its shard proposes nothing and still keeps its replica of the volumes
+        u32 first = 0;
+        for (u32 g = 0; g < G; ++g) {
+            const u32 cnt = N / G + (g < N % G ? 1u : 0u);
+            for (u32 n = first; (int)g == empty_range && n < first + cnt; ++n) {
+                p.valid[n >> 6] &= ~(1ull << (n & 63));
+                for (u32 c = 0; c < p.n_sc; ++c) p.sc[(size_t)c * p.Wn + (n >> 6)] &= ~(1ull << (n & 63));
+            }
+            first += cnt;
+        }
+    }
     State ref;
-    int rc = run_batch(p, ref, seed, B, order, feat, G, verbose, task_rows, my_rank);
+    int rc = run_batch(p, ref, seed, B, order, feat, G, verbose, task_rows, my_rank, feat >= 4 ? &mo : nullptr);
     if (rc || !churn) return rc;
     // the incremental path: drains, NodeInfo.removeTask, new tasks — then a second sharded batch over the same ranges
     Problem p2 = next_problem(p, ref);
@@ -199,8 +226,15 @@ int main(int argc, char** argv) {
     return run_batch(p2, ref2, seed, B, order, feat, G, verbose, task_rows, my_rank);
 }
 
-static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int feat, u32 G, bool verbose, bool task_rows, int my_rank) {
+static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int feat, u32 G, bool verbose, bool task_rows, int my_rank, const MountOpts* mo) {
     const u32 N = p.N, T = p.T, S = p.S;
+    const bool mounts = mo != nullptr;
+    VolProblem vp;
+    MountRun mr;
+    if (mounts) {
+        vp = make_volumes(seed, N, 8, 30);
+        mr = make_mounts(vp, seed, T, mo->every, mo->adjacent, 0, mo->last);
+    }
     std::set<i64> sc, sm;
     for (const RTask& r : p.rt)
         if (r.flags & RT_RES) { sc.insert(r.cpu); sm.insert(r.mem); }
@@ -217,7 +251,7 @@ static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int fea
     ref = initial_state(p);
     std::vector<u64> F;
     scan_window(p, ref, 0, T, F);
-    ref_window(p, ref, 0, T, F);
+    ref_window(p, ref, 0, T, F, mounts ? &mr : nullptr);
 
     // contiguous ranges of the canonical order, sizes differing by at most one
     std::vector<Shard> sh(G);
@@ -236,6 +270,20 @@ static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int fea
         s.prop.resize(B + (sizeof(R7Tail) + sizeof(R6Prop) - 1) / sizeof(R6Prop));
         max_words = std::max(max_words, s.p.Wn);
         first += cnt;
+    }
+    // a global node as shard g's replica writes it: its local index on the owner, the foreign code (owner, ITS local index) elsewhere
+    auto code_for = [&](u32 g) {
+        return [&sh, g, G](u32 n) {
+            u32 o = 0;
+            while (o + 1 < G && n >= sh[o + 1].first) ++o;
+            return o == g ? n - sh[o].first : (VOL_PIN_FOREIGN | (o << 26) | (n - sh[o].first));
+        };
+    };
+    for (u32 g = 0; mounts && g < G; ++g) {
+        Shard& s = sh[g];
+        s.vt = vol_tables(vp, s.first, s.p.N, code_for(g));
+        s.vrows.assign(std::max<size_t>(mr.csi_set.size(), 1) * s.p.Wn, 0x9999999999999999ull);
+        s.att.assign(std::max<size_t>(mr.csi_set.size(), 1) * VOL_MAX_MOUNTS, VOL_NONE);
     }
     for (u32 g = 0; g < G; ++g) {   // (pointers into the shards: taken once the vector of shards no longer moves)
         Shard& s = sh[g];
@@ -289,8 +337,17 @@ static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int fea
             a.rg_k0 = s.p.rg_k0.data();
             a.rg_k1 = s.p.rg_k1.data();
         }
+        if (mounts) {
+            a.csi_of = mr.csi_of.data();
+            a.csi_set = mr.csi_set.data();
+            a.vrows = s.vrows.data();
+            a.att = s.att.data();
+            a.vol = s.vt.view();
+            a.trail_out = reinterpret_cast<R7Tail*>(s.prop.data() + B)->slot;   // behind the shard's proposals: they travel with them
+        }
     }
     R7Args ma{};
+    ma.use_trailers = mounts ? 1u : 0u;
     ma.n_shards = G;
     ma.block = B;
     u32 hw = 0;
@@ -332,11 +389,25 @@ static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int fea
             memset(sh[g].prop.data(), 0xEE, (size_t)B * sizeof(R6Prop));
             emu::blockidx_y() = g;
             if (task_rows) grid((max_words + 3) / 4, 256, (size_t)B * 16, [ap]() { k_r7_taskrows(ap); });
+            if (mounts) {   // grid (words / 256, block, shards of the device)
+                emu::blockidx_z() = g;
+                for (u32 by = 0; by < B; ++by) {
+                    emu::blockidx_y() = by;
+                    grid((max_words + 255) / 256, 256, 0, [ap]() { k_r7_volrows(ap); });
+                }
+                emu::blockidx_z() = 0;
+                emu::blockidx_y() = g;
+            }
             grid(B, 64 * R6_PW, r6_propose_lds(max_words), [ap]() { k_r7_propose(ap); });
         }
         emu::blockidx_y() = 0;
-        grid(G, R6_COMMIT_THREADS, lds_commit, [ap, mp]() { k_r7_commit(ap, mp, 0u); });   // workgroup g: shard g
+        if (mounts) grid(G, R6_COMMIT_THREADS, lds_commit, [ap, mp]() { k_r7_commit_v(ap, mp, 0u); });
+        else grid(G, R6_COMMIT_THREADS, lds_commit, [ap, mp]() { k_r7_commit(ap, mp, 0u); });   // workgroup g: shard g
     };
+    u64 trail[2] = {0, 0}, cut_at_mount = 0, last_round_trailer = 0;   // trailers left per slot parity: every other shard takes each of them
+    std::set<u32> trail_owners;
+    u32 stalled = 0;
+    u64 stalls = 0;
     auto io_all = [](int fd, void* buf, size_t n, bool wr) {
         char* p = static_cast<char*>(buf);
         while (n) {
@@ -387,15 +458,28 @@ static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int fea
     while (sh[0].blk.pos < T) {
         const u32 before = sh[0].blk.pos;
         round();
+        last_round_trailer = 0;
+        for (u32 g = 0; mounts && g < G; ++g)
+            if (ma.tail[g]->slot[rounds & 1].valid) { trail[rounds & 1]++; trail_owners.insert(g); last_round_trailer = 1; }
+        if (mounts && sh[0].blk.pos < std::min(before + B, T) && mr.is(sh[0].blk.pos))
+            for (u32 j = before; j < sh[0].blk.pos; ++j)
+                if (mr.is(j)) { ++cut_at_mount; break; }
         ++rounds;
         for (u32 g = 0; g < G; ++g) {
+            if (mounts && sh[g].blk.rounds != rounds) { fprintf(stderr, "shard %u counts %u rounds, the driver %llu\n", g, sh[g].blk.rounds, (unsigned long long)rounds); return 3; }
             if (sh[g].blk.error) { fprintf(stderr, "shard %u reported error %u at task %u\n", g, sh[g].blk.error, sh[g].blk.pos); return 3; }
             if (sh[g].blk.pos != sh[0].blk.pos) { fprintf(stderr, "shard %u is at task %u, the leader at %u\n", g, sh[g].blk.pos, sh[0].blk.pos); return 3; }
         }
-        if (sh[0].blk.pos <= before) { fprintf(stderr, "no progress at task %u\n", before); return 3; }
+        // (a round that starts with a trailer decides no task with mounts: it stands still when the block's first task is one — never two in a row)
+        const bool may_stall = mounts && rounds >= 2 && stalled == 0 && mr.is(before);
+        if (sh[0].blk.pos <= before && !may_stall) { fprintf(stderr, "no progress at task %u\n", before); return 3; }
+        stalled = sh[0].blk.pos <= before ? 1u : 0u;
+        stalls += stalled;
     }
     round();   // a round past the end must be a no-op
     if (sh[0].blk.pos != T) return 3;
+    // behind the last round: every shard takes what that round's trailers say (launch_r7_settle)
+    if (mounts) grid(G, 64, 0, [ap, mp]() { k_r7_settle(ap, mp, 0u); });
 
     bool ok = true;
     std::vector<int32_t> out(T, -1);
@@ -426,6 +510,33 @@ static int run_batch(Problem& p, State& ref, u32 seed, u32 B, int order, int fea
         ok = ok && s.em.ctl.ncommit == ref.ctl.ncommit && s.em.ctl.ninf == ref.ctl.ninf;
         if (!ok) fprintf(stderr, "shard %u: ncommit %u (ref %u) ninf %u (ref %u)\n", g, s.em.ctl.ncommit, ref.ctl.ncommit, s.em.ctl.ninf, ref.ctl.ninf);
         ok = ok && same("inf_task", s.em.inf_task, ref.inf_task, ref.ctl.ninf) && same("inf_pos", s.em.inf_pos, ref.inf_pos, ref.ctl.ninf);
+    }
+    if (mounts) {
+        u64 foreign_pins = 0;
+        for (u32 g = 0; g < G && ok; ++g) {
+            const Shard& s = sh[g];
+            for (u32 j = 0; j < T && ok; ++j) {   // the attachment rows: on the shard that placed the task, nowhere else
+                if (!mr.is(j)) continue;
+                const u32 ck = mr.csi_of[j];
+                const bool owner = ref.out[j] >= (int32_t)s.first && ref.out[j] < (int32_t)(s.first + s.p.N);
+                for (u32 q = 0; q < VOL_MAX_MOUNTS && ok; ++q) {
+                    const u32 want = owner ? mr.att[(size_t)ck * VOL_MAX_MOUNTS + q] : VOL_NONE, got = s.att[(size_t)ck * VOL_MAX_MOUNTS + q];
+                    if (got != want) { fprintf(stderr, "MISMATCH att of task %u mount %u on shard %u: emu %d model %d\n", j, q, g, (int)got, (int)want); ok = false; }
+                }
+            }
+            for (u32 v = 0; v < vp.vol.size() && ok; ++v) {   // this replica's usage numbers
+                const VolDyn want = vp.derive(mr.use, v, code_for(g)), d = s.vt.vdyn[v];
+                if (want.n_tasks && want.pin < VOL_PIN_MANY && (want.pin & VOL_PIN_FOREIGN)) ++foreign_pins;
+                if (d.n_tasks != want.n_tasks || d.n_writers != want.n_writers || (want.n_tasks && d.pin != want.pin)) {
+                    fprintf(stderr, "MISMATCH usage of volume %u on shard %u: emu {%u tasks, %u writers, pin %08x} model {%u, %u, %08x}\n", v, g, d.n_tasks, d.n_writers, d.pin, want.n_tasks,
+                            want.n_writers, want.pin);
+                    ok = false;
+                }
+            }
+        }
+        fprintf(stderr, "reach mounts: tasks=%zu with_attachments=%llu failed_choice=%llu no_node=%llu cut_at_second_mount=%llu trailers_even=%llu trailers_odd=%llu trailer_owners=%zu last_round_trailer=%llu foreign_pins=%llu stalled_rounds=%llu\n",
+                mr.csi_set.size(), (unsigned long long)mr.with_att, (unsigned long long)mr.failed_choice, (unsigned long long)mr.no_node, (unsigned long long)cut_at_mount,
+                (unsigned long long)trail[0], (unsigned long long)trail[1], trail_owners.size(), (unsigned long long)last_round_trailer, (unsigned long long)foreign_pins, (unsigned long long)stalls);
     }
     if (verbose || !ok)
         fprintf(stderr, "seed %u N %u T %u S %u block %u order %d feat %d shards %u: placed %u inf %u | rounds %llu (%.1f tasks each) cut: exhausted %u exception %u uncounted %u -> %s\n", seed,

@@ -2,6 +2,7 @@
 workgroup, against the sequential model of tests/emu/emu_model.hpp: every output, every mutated array, and the level planes /
 demand-class rows the kernels maintain incrementally against a rebuild. No GPU involved; the GPU parity is tests/test_engine_blocks.py."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -16,7 +17,8 @@ CSRC = os.path.join(HERE, "..", "swarmkit_amd", "csrc")
 def emu_bin():
     os.makedirs(os.path.dirname(BIN), exist_ok=True)
     srcs = [os.path.join(EMU, "emu_resolve6.cpp"), os.path.join(EMU, "wv_emu.hpp"), os.path.join(EMU, "emu_model.hpp"),
-            os.path.join(CSRC, "swp_resolve6.hpp"), os.path.join(CSRC, "swp_shard.hpp"), os.path.join(CSRC, "swp_types.hpp")]
+            os.path.join(CSRC, "swp_resolve6.hpp"), os.path.join(CSRC, "swp_shard.hpp"), os.path.join(CSRC, "swp_types.hpp"),
+            os.path.join(CSRC, "swp_volumes.hpp")]
     if not os.path.exists(BIN) or any(os.path.getmtime(s) > os.path.getmtime(BIN) for s in srcs):
         tmp = BIN + ".%d.tmp" % os.getpid()   # (xdist workers may build at the same time)
         subprocess.run(["g++", "-O1", "-std=c++17", "-o", tmp, srcs[0]], check=True)
@@ -124,3 +126,49 @@ def test_under_random_wave_schedules(emu_bin, case, sched):
     r = subprocess.run([emu_bin] + args, capture_output=True, text=True, timeout=900, env=dict(os.environ, EMU_SCHED_SEED=str(sched)))
     assert r.returncode == 0, r.stderr[-2000:]
     assert "-> OK" in r.stderr
+
+
+# Feature level 4: tasks with cluster mounts (CSI volumes). (case, mount options): m<k> one task in k has a mount set, a: tasks 0 and 1
+# both have (two of them at a block's start), h: half of them want ONE single-node volume that start-up usage pins to the last node
+MOUNTS = [
+    ((31, 900, 1500, 40, 64, 0, 4, ""), ["m50", "a"]),        # rare
+    ((32, 700, 1200, 30, 64, 2, 4, ""), ["m2", "a"]),         # every second task: nearly every round is cut in front of the next one
+    ((33, 1000, 600, 40, 1, 2, 4, ""), ["m5", "a"]),          # a block of one task: no second task to cut in front of
+    ((34, 3000, 800, 100, 768, 0, 4, ""), ["m10", "a"]),      # a large block
+    ((35, 800, 1500, 30, 128, 1, 4, ""), ["m4", "a", "h"]),   # many tasks after one pinned single-node volume: on its node, or nowhere
+    ((36, 5000, 1500, 300, 256, 0, 4, "s"), ["m8", "a"]),     # two stretches with a rebuild between
+    ((37, 1200, 1000, 60, 64, 0, 4, "t"), ["m6", "a"]),       # task-rows mode
+    # w: half of them want to WRITE to a multi-node volume for one writer, two tasks in a row to the same one; rounds of dozens of tasks in
+    # a block of 512: the second writer sits in a LATER 64-task group of the block that decides the first — the cut must hold across groups
+    ((50, 10000, 2000, 20, 512, 1, 4, ""), ["m30", "w"]),
+]
+
+
+def check_mounts(case, opts, env=None):
+    r = subprocess.run([BIN] + [str(x) for x in case[:7]] + ["v"] + list(case[7]) + opts, capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "-> OK" in r.stderr
+    # what the MODEL's run came across (the cut count: rounds the driver saw end in front of a task with mounts after deciding one)
+    m = re.search(r"^reach mounts: (.*)$", r.stderr, re.M)
+    got = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", m.group(1))}
+    assert got["with_attachments"] > 0 and got["failed_choice"] + got["no_node"] > 0, got
+    if case[4] > 1:
+        assert got["cut_at_second_mount"] > 0, got
+    else:   # a block of one task never holds a second one
+        assert got["cut_at_second_mount"] == 0, got
+    if "h" in opts:
+        assert got["pinned_on_node"] > 0 and got["pinned_unplaced"] > 0 and got["pinned_elsewhere"] == 0, got
+
+
+@pytest.mark.parametrize("case,opts", MOUNTS, ids=lambda c: "seed%d-N%d-B%d-f%d%s" % (c[0], c[1], c[4], c[6], c[7]) if isinstance(c, tuple) else "".join(c))
+def test_tasks_with_cluster_mounts(emu_bin, case, opts):
+    """k_r6_volrows in front of each round and k_r6_commit_v, as swp_resolve6.hip launches them: a block decides at most one task with
+    mounts (its VolumesFilter row is of the round's start), the applying thread chooses and reserves. Against the model: placements,
+    every attachment row and every volume's final {tasks, writers, pin} derived from the model's (task, node, read-only) usages."""
+    check_mounts(case, opts)
+
+
+@pytest.mark.parametrize("case,opts,sched", [(MOUNTS[1][0], MOUNTS[1][1], 11), (MOUNTS[4][0], MOUNTS[4][1], 12), (MOUNTS[6][0], MOUNTS[6][1], 13)],
+                         ids=lambda c: "seed%d-N%d-B%d-f%d%s" % (c[0], c[1], c[4], c[6], c[7]) if isinstance(c, tuple) else "".join(c) if isinstance(c, list) else "sched%d" % c)
+def test_tasks_with_cluster_mounts_under_random_wave_schedules(emu_bin, case, opts, sched):
+    check_mounts(case, opts, env=dict(os.environ, EMU_SCHED_SEED=str(sched)))

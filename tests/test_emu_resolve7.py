@@ -6,6 +6,7 @@ shard's node rows, host ports, service rows, counters and the list of unplaceabl
 node set (tests/emu/emu_model.hpp). What a job of G GPUs computes — the one-device GPU tests run the same kernels with G engines
 (tests/test_engine_shards.py) — checked here without a GPU. TEST INFRASTRUCTURE around product source; no product code path uses it."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -20,7 +21,8 @@ BIN = os.path.join(HERE, "_build", "emu_resolve7")
 def emu_bin():
     os.makedirs(os.path.dirname(BIN), exist_ok=True)
     srcs = [os.path.join(EMU, "emu_resolve7.cpp"), os.path.join(EMU, "wv_emu.hpp"), os.path.join(EMU, "emu_model.hpp"),
-            os.path.join(CSRC, "swp_resolve6.hpp"), os.path.join(CSRC, "swp_resolve7.hpp"), os.path.join(CSRC, "swp_shard.hpp"), os.path.join(CSRC, "swp_types.hpp")]
+            os.path.join(CSRC, "swp_resolve6.hpp"), os.path.join(CSRC, "swp_resolve7.hpp"), os.path.join(CSRC, "swp_shard.hpp"), os.path.join(CSRC, "swp_types.hpp"),
+            os.path.join(CSRC, "swp_volumes.hpp")]
     if not os.path.exists(BIN) or any(os.path.getmtime(s) > os.path.getmtime(BIN) for s in srcs):
         tmp = BIN + ".%d.tmp" % os.getpid()   # (xdist workers may build at the same time)
         subprocess.run(["g++", "-O1", "-std=c++17", "-o", tmp, srcs[0]], check=True)
@@ -75,3 +77,45 @@ def test_under_random_wave_schedules(emu_bin, case, sched):
     r = subprocess.run([emu_bin] + args, capture_output=True, text=True, timeout=900, env=dict(os.environ, EMU_SCHED_SEED=str(sched)))
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stderr.count("-> OK") == (2 if "c" in case[8] else 1), r.stderr[-2000:]
+
+
+# Feature level 4: tasks with cluster mounts across node-range shards. m<k>: one task in k has a mount set; a: tasks 0 and 1 both have;
+# l: the batch's LAST task has one that every node serves — its reservation reaches the other replicas through k_r7_settle only;
+# e<g>: range g has no valid node. Start-up usage pins one single-node volume to node 0 (the first range) and one to the last node
+# (the last range): every other replica starts with the foreign code.
+MOUNTS = [
+    ((41, 600, 500, 30, 64, 0, 4, 3, ""), ["m6", "a", "l"]),
+    ((42, 700, 800, 30, 64, 2, 4, 2, ""), ["m4", "a", "l"]),
+    ((43, 1500, 600, 80, 128, 0, 4, 4, ""), ["m8", "a", "l", "e1"]),   # an empty range
+    ((44, 1200, 500, 60, 32, 1, 4, 8, ""), ["m5", "a", "l"]),          # the most shards a job has
+    ((45, 901, 700, 20, 64, 0, 4, 3, "t"), ["m3", "a", "l"]),          # task-rows mode
+]
+
+
+def check_mounts(binary, case, opts, env=None):
+    r = subprocess.run([binary] + [str(x) for x in case[:8]] + ["v"] + list(case[8]) + opts, capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stderr.count("-> OK") == 1, r.stderr[-2000:]
+    # counted by the MODEL's run, but for the protocol's own quantities (rounds cut in front of a second task with mounts, the trailers a
+    # round left per slot parity), which the driver reads between the rounds
+    m = re.search(r"^reach mounts: (.*)$", r.stderr, re.M)
+    got = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", m.group(1))}
+    assert got["with_attachments"] > 0 and got["failed_choice"] + got["no_node"] > 0 and got["cut_at_second_mount"] > 0, got
+    assert got["trailers_even"] > 0 and got["trailers_odd"] > 0 and got["trailer_owners"] >= 2, got   # both slots, from different shards
+    assert got["foreign_pins"] > 0, got              # a volume whose one node belongs to another shard, in the final replicas
+    assert got["last_round_trailer"] == 1, got       # the last round placed a task with mounts: only k_r7_settle tells the other replicas
+
+
+@pytest.mark.parametrize("case,opts", MOUNTS, ids=lambda c: "seed%d-N%d-B%d-f%d-G%d%s" % (c[0], c[1], c[4], c[6], c[7], c[8]) if isinstance(c, tuple) else "".join(c))
+def test_tasks_with_cluster_mounts_across_shards(emu_bin, case, opts):
+    """The volume protocol between shards: k_r7_volrows, k_r7_commit_v (the owner chooses, reserves and leaves a trailer in the slot of the
+    round's parity; every other shard takes it at the start of the next round with the foreign pin, and that round decides no task with
+    mounts), k_r7_settle behind the last round. Placements and attachment rows against the whole-set model; EVERY shard's final
+    {tasks, writers, pin} per volume against the numbers derived from the model's usages (the pin as that replica writes it)."""
+    check_mounts(emu_bin, case, opts)
+
+
+@pytest.mark.parametrize("case,opts,sched", [(MOUNTS[0][0], MOUNTS[0][1], 21), (MOUNTS[3][0], MOUNTS[3][1], 22)],
+                         ids=lambda c: "seed%d-N%d-B%d-f%d-G%d%s" % (c[0], c[1], c[4], c[6], c[7], c[8]) if isinstance(c, tuple) else "".join(c) if isinstance(c, list) else "sched%d" % c)
+def test_tasks_with_cluster_mounts_across_shards_under_random_wave_schedules(emu_bin, case, opts, sched):
+    check_mounts(emu_bin, case, opts, env=dict(os.environ, EMU_SCHED_SEED=str(sched)))
