@@ -526,7 +526,8 @@ int swp_fit_pairs_volumes(swp_engine*, const swp_task_desc* templates, uint32_t 
  * is gone, :152-168), else account the reservation against Description.Resources in that order and reject what no
  * longer fits (:172-184). The caller lists only ACTIVE nodes (:70-72) and resolves which constraint list applies;
  * an unparsable list is passed as constraint_set 0 (`constraints, _ := constraint.Parse`, :163). Tasks that carry
- * AssignedGenericResources (:188-199) stay on the Go path: do not pass their node.
+ * AssignedGenericResources (:188-199) stay on the Go path: do not pass their node — or pass everything to swp_enforce_generic below,
+ * which walks that last third of the loop too.
  *   out_reject[i] = 1 when task i would be set to REJECTED, else 0. */
 typedef struct {
     uint32_t node;          /* NODE_ID id; must be present in the engine's nodeSet mirror */
@@ -545,6 +546,31 @@ typedef struct {
 } swp_enforce_task;             /* 32 bytes */
 int swp_enforce(swp_engine*, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
                 uint8_t* out_reject);
+
+/* swp_enforce for nodes whose tasks hold AssignedGenericResources: the whole loop body (constraint_enforcer.go:65-202) in ONE
+ * sequential walk per node. The records of swp_enforce are unchanged; the generic resources travel in parallel arrays: per node its
+ * copy of Description.Resources.Generic (`available.Generic`, :109-111), per task its AssignedGenericResources, both in LIST ORDER.
+ * Entries node_res[node_res_off[i] .. node_res_off[i + 1]) belong to nodes[i], task_res[task_res_off[t] .. task_res_off[t + 1]) to tasks[t].
+ * Per task, after the state skips (:118-126): a constraint or cpu / mem rejection `continue`s WITHOUT claiming; a kept task with
+ * assignments is checked entry by entry with HasResource (api/genericresource/validate.go:54-85: the node's entries of the same kind in
+ * list order; a Discrete entry decides at once — false for a Named assignment, else value <= entry; a Named entry is false at once for
+ * a Discrete assignment, passed over for another name, true for the same name; list exhausted: false). The first failing entry sets
+ * out_reject[t] = 1 and ENDS THE NODE (`break loop`, :196-199): every later task of that node gets 0, whatever its constraints or
+ * reservations say. Otherwise the task claims (ConsumeNodeResources, helpers.go:58-111: every remaining node entry, in order, meets the
+ * task's entries of its kind, in order; Discrete meets Discrete: entry -= value, gone at <= 0, else on to the task's next entry;
+ * Named meets the same name: gone; a type mismatch or another name: ignored). An empty assignment list is nil. The walk is literal:
+ * a kind listed twice, or Discrete and Named entries under one kind, are taken as they stand.
+ * Validated first, all or nothing (out_reject is untouched on an error): offsets monotone, kind an id of SWP_SPACE_GENERIC_KIND,
+ * named 0 or 1 (SWP_EINVAL); nodes and task ranges as swp_enforce. Without any assignment the answer is swp_enforce's. */
+typedef struct {
+    uint32_t kind;    /* SWP_SPACE_GENERIC_KIND id */
+    uint32_t named;   /* 0: DiscreteResourceSpec, value = its Value (any int64, 0 and negatives included);
+                         1: NamedResourceSpec, value = an id the CALLER chooses for the string: equal strings <=> equal ids within this call */
+    int64_t  value;
+} swp_enforce_res;    /* 16 bytes */
+int swp_enforce_generic(swp_engine*, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
+                        const uint32_t* node_res_off /* [n_nodes + 1] */, const swp_enforce_res* node_res,
+                        const uint32_t* task_res_off /* [n_tasks + 1] */, const swp_enforce_res* task_res, uint8_t* out_reject);
 
 /* constraint.NodeMatches(service.constraints, node) for EVERY (constraint set, node) pair: the global orchestrator's
  * reconciliation sweeps (manager/orchestrator/global/global.go:306, :440, :513 — one NodeMatches per global service

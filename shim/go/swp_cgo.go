@@ -952,3 +952,48 @@ func (sch *Scheduler) rollbackSWP(failed []schedulingDecision) {
 // batches become sharded batches (the rounds on the devices, include/swp.h "node-range shards"; nodeset.go:57-120 is the scan they
 // distribute), task groups run on the set's union engine, tasks with cluster mounts included. A manager that runs one PROCESS per GPU
 // calls swp_rccl_unique_id / swp_rccl_init once and swp_shard_run_rank per batch instead (bench.py --gpus N is that deployment).
+
+// ---------------------------------------------------------------------------------------------- constraint enforcer
+// The enforcer (manager/orchestrator/constraintenforcer) shares the scheduler's engine: rejectNoncompliantTasksSWP in INTEGRATION.md
+// builds the records of its sweep and calls enforceSweep. Nodes whose tasks hold AssignedGenericResources go through the same call:
+// the loop's last third (constraint_enforcer.go:186-200) runs on the device too. Scheduler::enforce
+
+// enforceRes: a generic resource list as swp_enforce_res entries, LIST ORDER kept. A named value is an id handed out per sweep (`names`):
+// equal strings <=> equal ids. An entry with an empty oneof is left out (its Kind() is "" and nothing ever matches it).
+func (s *swpEngine) enforceRes(dst []C.swp_enforce_res, rs []*api.GenericResource, names map[string]C.int64_t) []C.swp_enforce_res {
+	for _, r := range rs {
+		if n := r.GetNamedResourceSpec(); n != nil {
+			id, ok := names[n.Value]
+			if !ok {
+				id = C.int64_t(len(names))
+				names[n.Value] = id
+			}
+			dst = append(dst, C.swp_enforce_res{kind: s.intern(C.SWP_SPACE_GENERIC_KIND, n.Kind), named: 1, value: id})
+		} else if d := r.GetDiscreteResourceSpec(); d != nil {
+			dst = append(dst, C.swp_enforce_res{kind: s.intern(C.SWP_SPACE_GENERIC_KIND, d.Kind), named: 0, value: C.int64_t(d.Value)})
+		}
+	}
+	return dst
+}
+
+// enforceSweep: one swp_enforce_generic call. nodeOff / taskOff: where each node's available.Generic and each task's
+// AssignedGenericResources lie in nodeRes / taskRes (one offset per record and one behind the last). reject[i] != 0: task i would be set
+// to REJECTED. An error leaves the caller on the reference's rejectNoncompliantTasks, node by node.
+func (s *swpEngine) enforceSweep(nodes []C.swp_enforce_node, tasks []C.swp_enforce_task, nodeOff []C.uint32_t, nodeRes []C.swp_enforce_res,
+	taskOff []C.uint32_t, taskRes []C.swp_enforce_res) ([]C.uint8_t, error) {
+	reject := make([]C.uint8_t, len(tasks))
+	if len(nodes) == 0 || len(tasks) == 0 {
+		return reject, nil
+	}
+	var nr, tr *C.swp_enforce_res // (an empty array: the offsets name no entry of it)
+	if len(nodeRes) > 0 {
+		nr = &nodeRes[0]
+	}
+	if len(taskRes) > 0 {
+		tr = &taskRes[0]
+	}
+	if rc := C.swp_enforce_generic(s.e, &nodes[0], C.uint32_t(len(nodes)), &tasks[0], C.uint32_t(len(tasks)), &nodeOff[0], nr, &taskOff[0], tr, &reject[0]); rc != C.SWP_OK {
+		return nil, s.err("swp_enforce_generic", rc)
+	}
+	return reject, nil
+}

@@ -86,6 +86,7 @@ PLACEMENT_DTYPE = np.dtype([("node", "<u4"), ("service", "<u4"), ("cpu", "<i8"),
 ENF_NODE_DTYPE = np.dtype([("node", "<u4"), ("first_task", "<u4"), ("n_tasks", "<u4"), ("reserved", "<u4"), ("cpu", "<i8"), ("mem", "<i8")])
 ENF_TASK_DTYPE = np.dtype([("cpu", "<i8"), ("mem", "<i8"), ("constraint_set", "<u4"), ("flags", "<u4"), ("desired_state", "<u4"), ("state", "<u4")])
 ENF_RESERVATIONS = 1
+ENF_RES_DTYPE = np.dtype([("kind", "<u4"), ("named", "<u4"), ("value", "<i8")])   # swp_enforce_res
 NODE_DYNAMIC_DTYPE = np.dtype([("node", "<u4"), ("flags", "<u4"), ("cpu", "<i8"), ("mem", "<i8"), ("total", "<u4"), ("reserved", "<u4")])
 NODE_ROW_DTYPE = np.dtype([("node", "<u4"), ("flags", "<u4"), ("cpu", "<i8"), ("mem", "<i8"), ("total", "<u4"), ("os", "<u4"), ("arch", "<u4"), ("os_fold", "<u4"),
                            ("arch_fold", "<u4"), ("hostname_fold", "<u4"), ("id_fold", "<u4"), ("reserved", "<u4"), ("ip", "u1", (16,)), ("version", "<u8")])
@@ -96,7 +97,7 @@ PROPOSAL_DTYPE = np.dtype([("level", "<u4"), ("n_cand", "<u4"), ("word", "<u4", 
                            ("exc_lo", "<u8"), ("exc_entry", "<u4"), ("flags", "<u4")])
 PICK_DTYPE = np.dtype([("shard", "<i4"), ("node", "<u4"), ("entry", "<u4"), ("reserved", "<u4")])
 assert PROPOSAL_DTYPE.itemsize == 80 and PICK_DTYPE.itemsize == 16
-assert ENF_NODE_DTYPE.itemsize == 32 and ENF_TASK_DTYPE.itemsize == 32
+assert ENF_NODE_DTYPE.itemsize == 32 and ENF_TASK_DTYPE.itemsize == 32 and ENF_RES_DTYPE.itemsize == 16
 assert TASK_DTYPE.itemsize == C.sizeof(TaskDesc) == 64
 assert PLACEMENT_DTYPE.itemsize == C.sizeof(Placement) == 32
 
@@ -110,7 +111,7 @@ EXPORTS = [
     "swp_create", "swp_destroy", "swp_reset", "swp_intern", "swp_intern_lookup", "swp_node_upsert", "swp_node_update_dynamic",
     "swp_node_remove", "swp_node_get", "swp_node_set_svc_count", "swp_node_get_svc_count", "swp_node_set_failures", "swp_node_port",
     "swp_constraint_set", "swp_platform_set", "swp_plugin_set", "swp_port_set", "swp_spread_set", "swp_schedule_groups", "swp_schedule_batch", "swp_batch_prepare",
-    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_node_matches",
+    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_enforce_generic", "swp_node_matches",
     "swp_stats", "swp_strerror", "swp_last_error", "swp_abi_check", "swp_node_update_dynamic_many", "swp_node_get_many", "swp_shardset_create",
     "swp_shard_begin", "swp_shard_propose", "swp_shard_merge", "swp_shard_commit", "swp_shard_end", "swp_shard_run", "swp_rccl_available", "swp_rccl_unique_id", "swp_rccl_init", "swp_rccl_finalize", "swp_shard_run_rank", "swp_shard_verdict",
     # include/swp_sched.h — the host layer above the engine
@@ -120,7 +121,7 @@ EXPORTS = [
     "swp_constraint_parse", "swp_key_equal_fold", "swp_explain", "swp_parse_ip",
 ]
 # exports a library built against this header may lack (the host layer's CPU test double): the host layer declares them weak
-OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes"}
+OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce_generic"}
 MAX_MOUNTS = 8              # SWP_MAX_MOUNTS
 NO_VOLUME = 0xFFFFFFFF      # SWP_NO_VOLUME
 FIT_NO_VOLUME = 8           # SWP_FIT_NO_VOLUME: swp_fit_pairs_volumes' first_fail for a failed chooseTaskVolumes
@@ -218,6 +219,7 @@ def load_library(path=None):
         "swp_fit_pairs": ([vp, vp, u32, vp, u32, vp], C.c_int),
         "swp_fit_pairs_volumes": ([vp, vp, u32, vp, u32, vp, vp], C.c_int),
         "swp_enforce": ([vp, vp, u32, vp, u32, vp], C.c_int),
+        "swp_enforce_generic": ([vp, vp, u32, vp, u32, vp, vp, vp, vp, vp], C.c_int),
         "swp_node_matches": ([vp, vp, u32, vp, u32], C.c_int),
         "swp_stats": ([vp, P(Stats)], C.c_int),
         "swp_strerror": ([C.c_int], cp),
@@ -553,6 +555,27 @@ class Engine:
         tasks = np.ascontiguousarray(tasks, dtype=ENF_TASK_DTYPE)
         out = np.zeros(len(tasks), dtype=np.uint8)
         self._ck(self.L.swp_enforce(self.h, nodes.ctypes.data, len(nodes), tasks.ctypes.data, len(tasks), out.ctypes.data))
+        return out
+
+    def enforce_generic(self, nodes, tasks, node_res_off, node_res, task_res_off, task_res, out=None):
+        """swp_enforce_generic: enforce with the sweep's generic half. node_res / task_res: ENF_RES_DTYPE, the nodes' available generic
+        resources and the tasks' AssignedGenericResources in list order; node_res_off [len(nodes) + 1] / task_res_off [len(tasks) + 1]:
+        where each node's / task's entries lie. out: a uint8 array to answer into (a refused call leaves it as it was)."""
+        nodes = np.ascontiguousarray(nodes, dtype=ENF_NODE_DTYPE)
+        tasks = np.ascontiguousarray(tasks, dtype=ENF_TASK_DTYPE)
+        node_res_off = np.ascontiguousarray(node_res_off, dtype=np.uint32)
+        task_res_off = np.ascontiguousarray(task_res_off, dtype=np.uint32)
+        node_res = np.ascontiguousarray(node_res, dtype=ENF_RES_DTYPE)
+        task_res = np.ascontiguousarray(task_res, dtype=ENF_RES_DTYPE)
+        if len(node_res_off) != len(nodes) + 1 or len(task_res_off) != len(tasks) + 1:
+            raise ValueError("one offset per node / task and one behind the last")
+        if (len(node_res_off) and int(node_res_off.max()) > len(node_res)) or (len(task_res_off) and int(task_res_off.max()) > len(task_res)):
+            raise ValueError("an offset lies beyond its array")
+        if out is None:
+            out = np.zeros(len(tasks), dtype=np.uint8)
+        assert out.dtype == np.uint8 and len(out) == len(tasks) and out.flags["C_CONTIGUOUS"]
+        self._ck(self.L.swp_enforce_generic(self.h, nodes.ctypes.data, len(nodes), tasks.ctypes.data, len(tasks), node_res_off.ctypes.data, node_res.ctypes.data,
+                                            task_res_off.ctypes.data, task_res.ctypes.data, out.ctypes.data))
         return out
 
     def node_matches(self, constraint_sets):

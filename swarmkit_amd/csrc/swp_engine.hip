@@ -2251,6 +2251,26 @@ int register_set(Index& index, Vec& sets, const std::string& key, Set&& value, u
 
 }  // namespace
 
+// What swp_enforce_generic refuses about its four parallel arrays before anything runs, for one engine and for a shard set alike
+// (n_kinds: the size of SWP_SPACE_GENERIC_KIND). The offsets are absolute positions in node_res / task_res.
+static int enforce_generic_check(swp_engine* e, uint32_t n_kinds, uint32_t n_nodes, uint32_t n_tasks, const uint32_t* node_res_off, const swp_enforce_res* node_res,
+                                 const uint32_t* task_res_off, const swp_enforce_res* task_res) {
+    struct Side { const char* what; uint32_t n; const uint32_t* off; const swp_enforce_res* res; };
+    const Side sides[2] = {{"node", n_nodes, node_res_off, node_res}, {"task", n_tasks, task_res_off, task_res}};
+    for (const Side& sd : sides) {
+        if (sd.n == 0) continue;
+        if (!sd.off) return e->fail(SWP_EINVAL, "enforce_generic: no %s offsets", sd.what);
+        for (uint32_t i = 0; i < sd.n; ++i)
+            if (sd.off[i + 1] < sd.off[i]) return e->fail(SWP_EINVAL, "enforce_generic: the %s offsets go down at %u (%u after %u)", sd.what, i + 1, sd.off[i + 1], sd.off[i]);
+        if (sd.off[sd.n] > sd.off[0] && !sd.res) return e->fail(SWP_EINVAL, "enforce_generic: the %s offsets name entries of an array that was not passed", sd.what);
+        for (uint32_t q = sd.off[0]; q < sd.off[sd.n]; ++q) {
+            if (sd.res[q].kind >= n_kinds) return e->fail(SWP_EINVAL, "enforce_generic: %s entry %u: unknown generic kind id %u", sd.what, q, sd.res[q].kind);
+            if (sd.res[q].named > 1u) return e->fail(SWP_EINVAL, "enforce_generic: %s entry %u: named = %u (0: Discrete, 1: Named)", sd.what, q, sd.res[q].named);
+        }
+    }
+    return SWP_OK;
+}
+
 // the shard set's side of every entry point (swp_shardset.hpp, included behind the extern "C" block)
 namespace ss {
 int create(const swp_config*, const int32_t*, uint32_t, uint32_t, swp_engine**);
@@ -2292,6 +2312,8 @@ int commit(swp_engine*, const swp_placement*, uint32_t, int);
 int check_node(swp_engine*, const swp_task_desc*, uint32_t, int32_t*);
 int fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*, uint32_t*);
 int enforce(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, uint8_t*);
+int enforce_generic(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, const uint32_t*, const swp_enforce_res*, const uint32_t*,
+                    const swp_enforce_res*, uint8_t*);
 int node_matches(swp_engine*, const uint32_t*, uint32_t, uint64_t*, uint32_t);
 int stats(swp_engine*, swp_stats_t*);
 }   // namespace ss
@@ -4498,6 +4520,115 @@ int swp_enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, 
     HIPCHECK(e, hipGetLastError());
     HIPCHECK(e, hipMemcpyAsync(out_reject, d_out.p, n_tasks, hipMemcpyDeviceToHost, st));
     HIPCHECK(e, hipStreamSynchronize(st));
+    return SWP_OK;
+}
+
+// swp_enforce with the sweep's last third (constraint_enforcer.go:186-200): the nodes none of whose tasks holds an assignment go to
+// k_enforce as in swp_enforce, every other node to one wave of k_enforce_generic (swp_enforce.hpp) with its list of available resources.
+int swp_enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
+                        const uint32_t* node_res_off, const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res,
+                        uint8_t* out_reject) {
+    if (e && e->set) return ss::enforce_generic(e, nodes, n_nodes, tasks, n_tasks, node_res_off, node_res, task_res_off, task_res, out_reject);
+    if (!e || (!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
+    if (int rc = enforce_generic_check(e, (uint32_t)e->spaces[SWP_SPACE_GENERIC_KIND].strs.size(), n_nodes, n_tasks, node_res_off, node_res, task_res_off, task_res)) return rc;
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        if (nodes[i].node >= e->nodes.size() || !e->nodes[nodes[i].node].present) return e->fail(SWP_ENOTFOUND, "enforce: node %u is not in the nodeSet mirror", nodes[i].node);
+        if ((uint64_t)nodes[i].first_task + nodes[i].n_tasks > n_tasks) return e->fail(SWP_EINVAL, "enforce: node %u lists tasks beyond the task array", i);
+    }
+    // the nodes with a task that holds an assignment, and whether one of their lists is longer than a wave
+    std::vector<uint32_t> gen_src;
+    bool long_list = false;
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        const uint32_t t0 = nodes[i].first_task, t1 = t0 + nodes[i].n_tasks;
+        if (t1 > t0 && task_res_off[t1] > task_res_off[t0]) {
+            gen_src.push_back(i);
+            long_list = long_list || node_res_off[i + 1] - node_res_off[i] > 64u;
+        }
+    }
+    if (gen_src.empty()) return swp_enforce(e, nodes, n_nodes, tasks, n_tasks, out_reject);
+    (void)hipSetDevice(e->device);
+    // the constraint classes as in swp_enforce: one pseudo task per enforce task
+    uint32_t svc = 0;
+    {
+        static const char kDummy[] = "\0swp-enforce";
+        int rc = swp_intern(e, SWP_SPACE_SERVICE, kDummy, sizeof kDummy - 1, &svc);
+        if (rc) return rc;
+    }
+    std::vector<swp_task_desc> descs(n_tasks);
+    std::memset(descs.data(), 0, descs.size() * sizeof(swp_task_desc));
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+        descs[i].service = svc;
+        descs[i].constraint_set = tasks[i].constraint_set;
+    }
+    int rc = flush_nodes(e);
+    if (rc) return rc;
+    swp_batch b;
+    if ((rc = build_batch(e, descs.data(), n_tasks, &b, nullptr))) return rc;
+    if ((rc = flush_nodes(e))) return rc;
+    if ((rc = upload_batch(e, &b))) return rc;
+    if ((rc = run_classes(e, &b))) return rc;
+    const uint32_t Wn = n_words_of(e->n_nodes);
+    // the node records: the plain nodes first (k_enforce's share), then the generic ones in gen_src's order
+    const uint32_t n_gen = (uint32_t)gen_src.size(), n_plain = n_nodes - n_gen;
+    std::vector<EnfNode> en(n_nodes);
+    {
+        uint32_t p = 0, g = 0;
+        for (uint32_t i = 0; i < n_nodes; ++i) {
+            const bool gen = g < n_gen && gen_src[g] == i;
+            en[gen ? n_plain + g++ : p++] = EnfNode{nodes[i].node, nodes[i].first_task, nodes[i].n_tasks, 0u, nodes[i].cpu, nodes[i].mem};
+        }
+    }
+    std::vector<EnfTask> et(n_tasks);
+    for (uint32_t i = 0; i < n_tasks; ++i)
+        et[i] = EnfTask{tasks[i].cpu, tasks[i].mem, b.rt[i].cls_con, tasks[i].flags & SWP_ENF_RESERVATIONS, tasks[i].desired_state, tasks[i].state};
+    static_assert(sizeof(swp_enforce_res) == sizeof(EnfRes), "swp_enforce_res is the device's record");
+    const size_t n_nres = node_res_off[n_nodes], n_tres = task_res_off[n_tasks];
+    DevBuf d_en, d_et, d_out, d_src, d_noff, d_nres, d_work, d_toff, d_tres;
+    if ((rc = upload(e, d_en, en))) return rc;
+    if ((rc = upload(e, d_et, et))) return rc;
+    if ((rc = upload(e, d_src, gen_src))) return rc;
+    hipStream_t st = e->stream;
+    auto put = [&](DevBuf& d, const void* src, size_t bytes) -> int {
+        HIPCHECK(e, d.reserve(std::max<size_t>(bytes, 16)));
+        if (bytes) HIPCHECK(e, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
+        return SWP_OK;
+    };
+    if ((rc = put(d_noff, node_res_off, ((size_t)n_nodes + 1) * 4))) return rc;
+    if ((rc = put(d_nres, node_res, n_nres * sizeof(EnfRes)))) return rc;
+    if ((rc = put(d_toff, task_res_off, ((size_t)n_tasks + 1) * 4))) return rc;
+    if ((rc = put(d_tres, task_res, n_tres * sizeof(EnfRes)))) return rc;
+    if (long_list) {   // the copy the waves of the long lists work on
+        HIPCHECK(e, d_work.reserve(n_nres * sizeof(EnfRes)));
+        HIPCHECK(e, hipMemcpyAsync(d_work.p, d_nres.p, n_nres * sizeof(EnfRes), hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHECK(e, d_out.reserve(n_tasks));
+    HIPCHECK(e, hipMemsetAsync(d_out.p, 0, n_tasks, st));
+    if (n_plain) {
+        hipLaunchKernelGGL(k_enforce, dim3((n_plain + 255) / 256), dim3(256), 0, st, n_plain, Wn, d_en.as<EnfNode>(), d_et.as<EnfTask>(), b.d_con.as<u64>(),
+                           d_out.as<unsigned char>());
+        HIPCHECK(e, hipGetLastError());
+    }
+    EnfGenArgs ga{};
+    ga.n_gen = n_gen;
+    ga.n_words = Wn;
+    ga.nodes = d_en.as<EnfNode>() + n_plain;
+    ga.src = d_src.as<u32>();
+    ga.tasks = d_et.as<EnfTask>();
+    ga.con = b.d_con.as<u64>();
+    ga.node_res_off = d_noff.as<u32>();
+    ga.node_res = d_nres.as<EnfRes>();
+    ga.work = long_list ? d_work.as<EnfRes>() : nullptr;
+    ga.task_res_off = d_toff.as<u32>();
+    ga.task_res = d_tres.as<EnfRes>();
+    ga.out = d_out.as<unsigned char>();
+    {
+        hipError_t r = launch_enforce_generic(ga, st);
+        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_enforce_generic launch: %s", hipGetErrorString(r));
+    }
+    std::vector<uint8_t> rej(n_tasks);   // (out_reject stays as it was unless the whole call succeeds)
+    HIPCHECK(e, hipMemcpyAsync(rej.data(), d_out.p, n_tasks, hipMemcpyDeviceToHost, st));
+    HIPCHECK(e, hipStreamSynchronize(st));
+    std::memcpy(out_reject, rej.data(), n_tasks);
     return SWP_OK;
 }
 

@@ -27,6 +27,10 @@ hipError_t launch_vol_choose(const VolChooseArgs& a, hipStream_t s);
 struct FitVolArgs;
 hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s);   // k_fit_pairs_vol (swp_fitpairs.hpp)
 
+// the enforcer sweep's nodes with a generic task (swp_enforce.hpp, built in swp_resolve6.hip): one wave per node
+struct EnfGenArgs;
+hipError_t launch_enforce_generic(const EnfGenArgs& a, hipStream_t s);
+
 // node-range shards, rounds on the device (swp_resolve7.hpp, built in swp_resolve6.hip)
 struct R7Args;
 size_t r7_commit_lds_size(uint32_t hw_total, uint32_t block, uint32_t n_rr);

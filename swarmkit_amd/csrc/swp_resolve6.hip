@@ -10,6 +10,8 @@
 #include "swp_resolve6.hpp"
 #include "swp_resolve7.hpp"
 #include "swp_fitpairs.hpp"
+#define SWP_ENF_KERNELS
+#include "swp_enforce.hpp"
 #define SWP_SCAN_KERNELS
 #include "swp_scan.hpp"
 
@@ -76,6 +78,13 @@ hipError_t launch_vol_choose(const VolChooseArgs& a, hipStream_t s) {
 hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s) {
     if (a.f.n_seg == 0) return hipSuccess;
     hipLaunchKernelGGL(k_fit_pairs_vol, dim3((a.f.n_seg + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// the enforcer sweep's nodes with a generic task (swp_enforce.hpp): one wave per node, four to a workgroup
+hipError_t launch_enforce_generic(const EnfGenArgs& a, hipStream_t s) {
+    if (a.n_gen == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_enforce_generic, dim3((a.n_gen + 3) / 4), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -40,6 +40,9 @@
 extern "C" int swp_fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*) __attribute__((weak));
 // Weak as well: with it a task with cluster mounts joins the run; without it such a task keeps the per-task path and ends the run in front of it.
 extern "C" int swp_fit_pairs_volumes(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*, uint32_t*) __attribute__((weak));
+// Weak as well: with it the enforcer sweep judges assigned generic resources in the same engine call; without it the host walks those nodes after swp_enforce.
+extern "C" int swp_enforce_generic(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, const uint32_t*, const swp_enforce_res*, const uint32_t*,
+                                   const swp_enforce_res*, uint8_t*) __attribute__((weak));
 
 namespace swp {
 
@@ -1532,7 +1535,8 @@ class Scheduler {
     }
 
     // ---------------------------------------------------------------------------------------------- constraint enforcer
-    // constraintenforcer.rejectNoncompliantTasks for many nodes (constraint_enforcer.go:65-196) through swp_enforce.
+    // constraintenforcer.rejectNoncompliantTasks for many nodes (constraint_enforcer.go:65-202) through swp_enforce — or, when a listed
+    // task holds AssignedGenericResources and the engine has the entry, through ONE swp_enforce_generic call.
     Value enforce(const Value& req) {
         const Value* node_docs = req.get("nodes");
         const Value* tbn = req.get("tasks_by_node");
@@ -1540,7 +1544,7 @@ class Scheduler {
         std::vector<swp_enforce_node> nrec;
         std::vector<swp_enforce_task> trec;
         std::vector<std::pair<std::string, std::string>> owners;
-        struct GenericWalk { std::string nid; uint32_t first; generic::List avail; std::vector<generic::List> assigned; std::vector<bool> has; };
+        struct GenericWalk { std::string nid; uint32_t pos, first; generic::List avail; std::vector<generic::List> assigned; std::vector<bool> has; };
         std::vector<GenericWalk> walks;
         Value out = Value::object();
         if (node_docs == nullptr || !node_docs->is_arr()) return out;
@@ -1553,13 +1557,14 @@ class Scheduler {
                     for (const Value& t : *lst->a) tasks.push_back(&t);
             std::stable_sort(tasks.begin(), tasks.end(), [](const Value* a, const Value* b) { return task_id(*a) < task_id(*b); });
             const Value* res = at(&nd, "Description", "Resources");
-            // The generic half (constraint_enforcer.go:186-200) is walked on the host AFTER the device call (below): the device's verdicts
-            // — constraints, then memory and cpu accounted task by task — do not depend on it.
+            // The generic half (constraint_enforcer.go:186-200) goes to the device with swp_enforce_generic; over an engine without that entry it
+            // is walked on the host AFTER swp_enforce (below): those verdicts — constraints, then memory and cpu accounted task by task — do not depend on it.
             bool generic = false;
             for (const Value* t : tasks) generic = generic || t->get("AssignedGenericResources") != nullptr;
             if (generic) {
                 GenericWalk w;
                 w.nid = nid;
+                w.pos = (uint32_t)nrec.size();
                 w.first = (uint32_t)trec.size();
                 w.avail = generic::decode(res != nullptr ? res->get("Generic") : nullptr);
                 for (const Value* t : tasks) {
@@ -1603,7 +1608,38 @@ class Scheduler {
         }
         if (trec.empty()) return out;
         std::vector<uint8_t> rej(trec.size(), 0);
-        ck(swp_enforce(e_, nrec.data(), (uint32_t)nrec.size(), trec.data(), (uint32_t)trec.size(), rej.data()), "swp_enforce");
+        bool assignments = false;
+        for (const GenericWalk& w : walks)
+            for (const generic::List& a : w.assigned) assignments = assignments || !a.empty();
+        if (assignments && swp_enforce_generic != nullptr) {
+            // :186-200 in the same engine call: the lists travel next to the records, in list order; a name is an id of this call
+            std::vector<uint32_t> noff(nrec.size() + 1, 0), toff(trec.size() + 1, 0);
+            std::vector<swp_enforce_res> nres, tres;
+            std::unordered_map<std::string, int64_t> names;
+            auto put = [&](std::vector<swp_enforce_res>& out, const generic::List& l) {
+                for (const generic::Res& r : l) {
+                    swp_enforce_res x;
+                    x.kind = intern(SWP_SPACE_GENERIC_KIND, r.kind);
+                    x.named = r.named ? 1u : 0u;
+                    x.value = r.named ? names.emplace(r.sval, (int64_t)names.size()).first->second : r.ival;
+                    out.push_back(x);
+                }
+            };
+            for (const GenericWalk& w : walks) {
+                put(nres, w.avail);
+                noff[w.pos + 1] = (uint32_t)w.avail.size();
+                for (size_t k = 0; k < w.assigned.size(); ++k) {
+                    put(tres, w.assigned[k]);
+                    toff[w.first + k + 1] = (uint32_t)w.assigned[k].size();
+                }
+            }
+            for (size_t i = 1; i < noff.size(); ++i) noff[i] += noff[i - 1];   // (the walks come in node order, their tasks in task order)
+            for (size_t i = 1; i < toff.size(); ++i) toff[i] += toff[i - 1];
+            ck(swp_enforce_generic(e_, nrec.data(), (uint32_t)nrec.size(), trec.data(), (uint32_t)trec.size(), noff.data(), nres.data(), toff.data(), tres.data(), rej.data()),
+               "swp_enforce_generic");
+            walks.clear();
+        } else
+            ck(swp_enforce(e_, nrec.data(), (uint32_t)nrec.size(), trec.data(), (uint32_t)trec.size(), rej.data()), "swp_enforce");
         // :186-200 for the nodes whose tasks hold generic resources: a task the device kept claims what it was assigned from the node's
         // list (ClaimResources against a throw-away store); the first task whose assignment is no longer there is rejected and ENDS the
         // node's loop (`break loop`): nothing behind it is looked at, whatever the device said about it.

@@ -682,6 +682,55 @@ int enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, cons
     return SWP_OK;
 }
 
+// swp_enforce_generic: split by the owner of each node as enforce above; every part carries its slices of the four arrays (offsets
+// rebased). Everything a shard would refuse is refused here first, and the verdicts reach out_reject only when every shard has answered.
+int enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks, const uint32_t* node_res_off,
+                    const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res, uint8_t* out_reject) {
+    ShardSet& S = *e->set;
+    if ((!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
+    if (S.broken) return broken_error(e);
+    if (int rc = enforce_generic_check(e, (uint32_t)S.sh[0]->spaces[SWP_SPACE_GENERIC_KIND].strs.size(), n_nodes, n_tasks, node_res_off, node_res, task_res_off, task_res)) return rc;
+    struct Part {
+        std::vector<swp_enforce_node> nodes;
+        std::vector<swp_enforce_task> tasks;
+        std::vector<uint32_t> src, noff{0u}, toff{0u};
+        std::vector<swp_enforce_res> nres, tres;
+    };
+    std::vector<Part> per(S.sh.size());
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        uint32_t g = 0, l = 0;
+        if (!locate(S, nodes[i].node, &g, &l) || l >= S.sh[g]->nodes.size() || !S.sh[g]->nodes[l].present)
+            return e->fail(SWP_ENOTFOUND, "enforce: node %u is not in the nodeSet mirror", nodes[i].node);
+        if ((uint64_t)nodes[i].first_task + nodes[i].n_tasks > n_tasks) return e->fail(SWP_EINVAL, "enforce: node %u lists tasks beyond the task array", i);
+        Part& P = per[g];
+        swp_enforce_node q = nodes[i];
+        q.node = l;
+        q.first_task = (uint32_t)P.tasks.size();
+        for (uint32_t k = 0; k < nodes[i].n_tasks; ++k) {
+            const uint32_t t = nodes[i].first_task + k;
+            P.tasks.push_back(tasks[t]);
+            P.src.push_back(t);
+            P.tres.insert(P.tres.end(), task_res + task_res_off[t], task_res + task_res_off[t + 1]);
+            P.toff.push_back((uint32_t)P.tres.size());
+        }
+        P.nodes.push_back(q);
+        P.nres.insert(P.nres.end(), node_res + node_res_off[i], node_res + node_res_off[i + 1]);
+        P.noff.push_back((uint32_t)P.nres.size());
+    }
+    std::vector<uint8_t> all(n_tasks, 0), rej;
+    for (size_t g = 0; g < per.size(); ++g) {
+        Part& P = per[g];
+        if (P.tasks.empty()) continue;
+        rej.assign(P.tasks.size(), 0);
+        if (int rc = swp_enforce_generic(S.sh[g], P.nodes.data(), (uint32_t)P.nodes.size(), P.tasks.data(), (uint32_t)P.tasks.size(), P.noff.data(), P.nres.data(),
+                                         P.toff.data(), P.tres.data(), rej.data()))
+            return take_error(e, S.sh[g], rc);
+        for (size_t k = 0; k < rej.size(); ++k) all[P.src[k]] = rej[k];
+    }
+    if (n_tasks) std::memcpy(out_reject, all.data(), n_tasks);
+    return SWP_OK;
+}
+
 int node_matches(swp_engine* e, const uint32_t* sets, uint32_t n_sets, uint64_t* out, uint32_t n_words) {
     ShardSet& S = *e->set;
     if ((!sets && n_sets) || (!out && n_sets)) return SWP_EINVAL;
