@@ -528,7 +528,9 @@ int swp_fit_pairs_volumes(swp_engine*, const swp_task_desc* templates, uint32_t 
  * an unparsable list is passed as constraint_set 0 (`constraints, _ := constraint.Parse`, :163). Tasks that carry
  * AssignedGenericResources (:188-199) stay on the Go path: do not pass their node — or pass everything to swp_enforce_generic below,
  * which walks that last third of the loop too.
- *   out_reject[i] = 1 when task i would be set to REJECTED, else 0. */
+ *   out_reject[i] = 1 when task i would be set to REJECTED, else 0. All or nothing, as swp_enforce_generic: out_reject is written
+ *   only when the whole call succeeds — a refused call (a node that is not in the mirror, a task range beyond the array, a device
+ *   error), on one engine or on a shard set, leaves it as the caller filled it. */
 typedef struct {
     uint32_t node;          /* NODE_ID id; must be present in the engine's nodeSet mirror */
     uint32_t first_task;    /* index of the node's first task in `tasks` */

@@ -548,12 +548,15 @@ class Engine:
         self._ck(self.L.swp_schedule_groups(self.h, groups.ctypes.data, sizes.ctypes.data, len(groups), out.ctypes.data, hist.ctypes.data))
         return out, hist
 
-    def enforce(self, nodes, tasks):
+    def enforce(self, nodes, tasks, out=None):
         """constraintenforcer.rejectNoncompliantTasks over many nodes. nodes: ENF_NODE_DTYPE, tasks: ENF_TASK_DTYPE
-        (grouped by node, store order). Returns uint8[len(tasks)]: 1 = the task would be REJECTED."""
+        (grouped by node, store order). Returns uint8[len(tasks)]: 1 = the task would be REJECTED. out: a uint8 array to answer into
+        (a refused call leaves it as it was)."""
         nodes = np.ascontiguousarray(nodes, dtype=ENF_NODE_DTYPE)
         tasks = np.ascontiguousarray(tasks, dtype=ENF_TASK_DTYPE)
-        out = np.zeros(len(tasks), dtype=np.uint8)
+        if out is None:
+            out = np.zeros(len(tasks), dtype=np.uint8)
+        assert out.dtype == np.uint8 and len(out) == len(tasks) and out.flags["C_CONTIGUOUS"]
         self._ck(self.L.swp_enforce(self.h, nodes.ctypes.data, len(nodes), tasks.ctypes.data, len(tasks), out.ctypes.data))
         return out
 

@@ -809,87 +809,18 @@ struct CheckArgs {
     int32_t gval[8];
     const int32_t* gcnt;
 };
+// (the chain itself: fit_first_fail, swp_fitpairs.hpp, shared with the preassigned pair pass; -2: the node is outside `valid`)
 __global__ void k_check_pair(CheckArgs a) {
     if (threadIdx.x != 0) return;
-    u32 n = a.node, w = n >> 6;
-    u64 bit = 1ull << (n & 63);
-    int ff = -1;
-    if (!(a.valid[w] & bit)) ff = -2;
-    else if (!(a.ready[w] & bit)) ff = 0;
-    else if ((a.rt.flags & RT_RES) && !(a.rt.cpu <= a.cpu[n] && a.rt.mem <= a.mem[n])) ff = 1;
-    else if ((a.rt.flags & RT_RES) && [&] {
-                 for (u32 g = 0; g < a.n_gen; ++g)
-                     if (a.gcnt[(size_t)a.gkind[g] * a.gstride + n] < a.gval[g]) return true;   // HasEnough, validate.go:24-52
-                 return false;
-             }())
-        ff = 1;
-    else if (a.rt.cls_plug && !(a.plug[(size_t)a.rt.cls_plug * a.n_words + w] & bit)) ff = 2;
-    else if (a.rt.cls_con && !(a.con[(size_t)a.rt.cls_con * a.n_words + w] & bit)) ff = 3;
-    else if (a.rt.cls_plat && !(a.plat[(size_t)a.rt.cls_plat * a.n_words + w] & bit)) ff = 4;
-    else if ((a.rt.flags & RT_PORTS) && a.port_busy) ff = 5;
-    else if ((a.rt.flags & RT_MAXREP) && !((u64)a.svc_count < a.rt.maxrep)) ff = 6;
-    *a.out = ff;
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_fit_pairs — taskFitNode for many preassigned tasks (processPreassignedTasks, scheduler.go:398-426, 646-690).
-// The pairs come grouped by node (segments, pair order kept inside each); one thread walks one segment in order and judges every
-// pair with k_check_pair's chain against the node as the earlier passing pairs of the segment left it (NodeInfo.addTask between
-// two tasks): cpu / mem in registers, the generic counts, host-port claims and per-service counts in slots of its own. Different
-// nodes are independent. The thread is the only writer of its node, its slots and its pairs' verdicts: plain loads and stores.
-// ---------------------------------------------------------------------------------------------
-// (FitTmpl, FitPair, FitArgs: swp_fitpairs.hpp, shared with the mount sibling k_fit_pairs_vol)
-__global__ __launch_bounds__(256) void k_fit_pairs(FitArgs a) {
-    const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= a.n_seg) return;
-    // (the host passes present nodes only: DEV_VALID is set for every one of them, k_check_pair's -2 cannot happen here)
-    const u32 n = a.seg_node[s], w = n >> 6;
+    const u32 n = a.node, w = n >> 6;
     const u64 bit = 1ull << (n & 63);
-    const bool ready = (a.ready[w] & bit) != 0;
-    i64 cpu = a.cpu[n], mem = a.mem[n];
-    u32 total = a.total[n];
-    const u32 p1 = a.seg_off[s + 1];
-    for (u32 p = a.seg_off[s]; p < p1; ++p) {
-        const FitPair q = a.pairs[p];
-        const FitTmpl& t = a.tm[q.tmpl];
-        const u32 fl = t.rt.flags;
-        int ff = -1;
-        if (!ready) ff = 0;
-        else if ((fl & RT_RES) && !(t.rt.cpu <= cpu && t.rt.mem <= mem)) ff = 1;
-        else if ((fl & RT_RES) && [&] {
-                     for (u32 g = 0; g < t.n_gen; ++g)
-                         if (a.gcnt[(size_t)a.gkind[t.gen_off + g] * a.gstride + n] < a.gval[t.gen_off + g]) return true;   // HasEnough, validate.go:24-52
-                     return false;
-                 }())
-            ff = 1;
-        else if (t.rt.cls_plug && !(a.plug[(size_t)t.rt.cls_plug * a.n_words + w] & bit)) ff = 2;
-        else if (t.rt.cls_con && !(a.con[(size_t)t.rt.cls_con * a.n_words + w] & bit)) ff = 3;
-        else if (t.rt.cls_plat && !(a.plat[(size_t)t.rt.cls_plat * a.n_words + w] & bit)) ff = 4;
-        else if ((fl & RT_PORTS) && [&] {
-                     for (u32 k = 0; k < t.n_ports; ++k)
-                         if (a.port_taken[a.port_slot[q.port_off + k]]) return true;   // HostPortFilter, filter.go:335-350
-                     return false;
-                 }())
-            ff = 5;
-        else if ((fl & RT_MAXREP) && !((u64)a.svc_cnt[q.svc_slot] < t.rt.maxrep)) ff = 6;
-        a.out[q.idx] = ff;
-        if (ff != -1) continue;
-        // NodeInfo.addTask (nodeinfo.go:128-154): what a placement of swp_schedule_batch books
-        cpu -= t.rt.cpu;
-        mem -= t.rt.mem;
-        for (u32 g = 0; g < t.n_gen; ++g) {
-            int32_t* c = a.gcnt + (size_t)a.gkind[t.gen_off + g] * a.gstride + n;
-            *c = max(*c - a.gval[t.gen_off + g], 0);   // (an entry that reaches 0 leaves the list)
-        }
-        if (!(fl & RT_UNCOUNTED)) {
-            ++total;
-            ++a.svc_cnt[q.svc_slot];
-        }
-        for (u32 k = 0; k < t.n_ports; ++k) a.port_taken[a.port_slot[q.port_off + k]] = 1u;
+    if (!(a.valid[w] & bit)) {
+        *a.out = -2;
+        return;
     }
-    a.cpu[n] = cpu;
-    a.mem[n] = mem;
-    a.total[n] = total;
+    *a.out = fit_first_fail(
+        a.rt, n, a.n_words, (a.ready[w] & bit) != 0, a.cpu[n], a.mem[n], a.n_gen, a.gkind, a.gval, a.gcnt, a.gstride, a.plug, a.con, a.plat,
+        [&] { return a.port_busy != 0; }, [&] { return a.svc_count; });
 }
 
 }  // namespace swpdev

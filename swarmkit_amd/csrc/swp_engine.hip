@@ -2271,6 +2271,50 @@ static int enforce_generic_check(swp_engine* e, uint32_t n_kinds, uint32_t n_nod
     return SWP_OK;
 }
 
+// The service the enforcer's pseudo tasks carry, and the classes of a list of constraint sets exactly as a scheduling batch gets them:
+// one pseudo task per entry of `sets`. On return `b` is uploaded and its classes are run — entry i's row of b->d_con is b->rt[i].cls_con
+// (0: no constraints). What swp_enforce, swp_enforce_generic and swp_node_matches share.
+static int intern_enforce_service(swp_engine* e, uint32_t* id_out) {
+    static const char kService[] = "\0swp-enforce";
+    return swp_intern(e, SWP_SPACE_SERVICE, kService, sizeof kService - 1, id_out);
+}
+static int constraint_classes(swp_engine* e, const uint32_t* sets, uint32_t n, swp_batch* b) {
+    uint32_t svc = 0;
+    int rc = intern_enforce_service(e, &svc);
+    if (rc) return rc;
+    std::vector<swp_task_desc> descs(n);
+    std::memset(descs.data(), 0, descs.size() * sizeof(swp_task_desc));
+    for (uint32_t i = 0; i < n; ++i) {
+        descs[i].service = svc;
+        descs[i].constraint_set = sets[i];
+    }
+    if ((rc = flush_nodes(e))) return rc;
+    if ((rc = build_batch(e, descs.data(), n, b, nullptr))) return rc;
+    if ((rc = flush_nodes(e))) return rc;
+    if ((rc = upload_batch(e, b))) return rc;
+    return run_classes(e, b);
+}
+
+// What swp_fit_pairs / swp_fit_pairs_volumes (with_mounts) refuse about their templates before anything runs, for one engine and for a
+// shard set alike: `e` reports, `tables` is the engine whose predicate sets and ids are consulted (a set's are replicated: any shard's).
+static int fit_templates_check(swp_engine* e, const swp_engine* tables, const swp_task_desc* templates, uint32_t n_templates, bool with_mounts, bool* any_mounts) {
+    for (uint32_t t = 0; t < n_templates; ++t) {
+        const swp_task_desc& d = templates[t];
+        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) {
+            if (!with_mounts) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
+            if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) >= tables->mount_sets.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown mount set", t);
+            *any_mounts = true;
+        }
+        if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
+        if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
+        if (d.service >= tables->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
+        if (d.constraint_set >= tables->con_sets.size() || d.platform_set >= tables->plat_sets.size() || d.plugin_set >= tables->plug_sets.size() ||
+            d.port_set >= tables->port_sets.size() || d.generic_set >= tables->gen_sets.size())
+            return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown predicate set", t);
+    }
+    return SWP_OK;
+}
+
 // the shard set's side of every entry point (swp_shardset.hpp, included behind the extern "C" block)
 namespace ss {
 int create(const swp_config*, const int32_t*, uint32_t, uint32_t, swp_engine**);
@@ -2311,9 +2355,8 @@ int state_restore(swp_engine*);
 int commit(swp_engine*, const swp_placement*, uint32_t, int);
 int check_node(swp_engine*, const swp_task_desc*, uint32_t, int32_t*);
 int fit_pairs(swp_engine*, const swp_task_desc*, uint32_t, const swp_fit_pair*, uint32_t, int32_t*, uint32_t*);
-int enforce(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, uint8_t*);
 int enforce_generic(swp_engine*, const swp_enforce_node*, uint32_t, const swp_enforce_task*, uint32_t, const uint32_t*, const swp_enforce_res*, const uint32_t*,
-                    const swp_enforce_res*, uint8_t*);
+                    const swp_enforce_res*, uint8_t*, bool plain);
 int node_matches(swp_engine*, const uint32_t*, uint32_t, uint64_t*, uint32_t);
 int stats(swp_engine*, swp_stats_t*);
 }   // namespace ss
@@ -4249,7 +4292,6 @@ int swp_check_node(swp_engine* e, const swp_task_desc* task, uint32_t node, int3
     HIPCHECK(e, hipStreamSynchronize(e->stream));
     *first_fail = ff;
     if (ff < 0 && (task->flags >> SWP_TASK_MOUNTS_SHIFT)) {   // VolumesFilter, the pipeline's last entry: any mount with a volume on the node
-        uint32_t att[SWP_MAX_MOUNTS], na = 0;
         if (!e->has_volumes() || e->volumes.empty()) { *first_fail = 7; return SWP_OK; }
         DevBuf d;
         HIPCHECK(e, d.reserve((SWP_MAX_MOUNTS + 3) * 4));
@@ -4263,8 +4305,6 @@ int swp_check_node(swp_engine* e, const swp_task_desc* task, uint32_t node, int3
         uint32_t h[SWP_MAX_MOUNTS + 3];
         HIPCHECK(e, hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, e->stream));
         HIPCHECK(e, hipStreamSynchronize(e->stream));
-        (void)att;
-        (void)na;
         if (!h[SWP_MAX_MOUNTS + 2]) *first_fail = 7;
     }
     return SWP_OK;
@@ -4278,20 +4318,7 @@ static int fit_pairs_impl(swp_engine* e, const swp_task_desc* templates, uint32_
     if (n_pairs == 0) return SWP_OK;
     // everything is checked before the device is touched: a refused call leaves the mirror as it was
     bool any_mounts = false;
-    for (uint32_t t = 0; t < n_templates; ++t) {
-        const swp_task_desc& d = templates[t];
-        if (d.flags >> SWP_TASK_MOUNTS_SHIFT) {
-            if (!out_att) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
-            if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) >= e->mount_sets.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown mount set", t);
-            any_mounts = true;
-        }
-        if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
-        if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
-        if (d.service >= e->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
-        if (d.constraint_set >= e->con_sets.size() || d.platform_set >= e->plat_sets.size() || d.plugin_set >= e->plug_sets.size() ||
-            d.port_set >= e->port_sets.size() || d.generic_set >= e->gen_sets.size())
-            return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown predicate set", t);
-    }
+    if (int rc = fit_templates_check(e, e, templates, n_templates, out_att != nullptr, &any_mounts)) return rc;
     const uint32_t NN = (uint32_t)e->nodes.size();
     for (uint32_t i = 0; i < n_pairs; ++i) {
         if (pairs[i].tmpl >= n_templates) return e->fail(SWP_EINVAL, "fit_pairs: pair %u names template %u of %u", i, pairs[i].tmpl, n_templates);
@@ -4434,8 +4461,8 @@ static int fit_pairs_impl(swp_engine* e, const swp_task_desc* templates, uint32_
         if (r != hipSuccess) return e->fail(SWP_EHIP, "k_fit_pairs_vol launch: %s", hipGetErrorString(r));
         HIPCHECK(e, hipMemcpyAsync(out_att, base + o_att, (size_t)n_pairs * SWP_MAX_MOUNTS * 4, hipMemcpyDeviceToHost, e->stream));
     } else {
-        hipLaunchKernelGGL(k_fit_pairs, dim3((n_seg + 255) / 256), dim3(256), 0, e->stream, fa);
-        HIPCHECK(e, hipGetLastError());
+        hipError_t r = launch_fit_pairs(fa, e->stream);
+        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_fit_pairs launch: %s", hipGetErrorString(r));
         if (out_att) std::fill(out_att, out_att + (size_t)n_pairs * SWP_MAX_MOUNTS, SWP_NO_VOLUME);
     }
     HIPCHECK(e, hipMemcpyAsync(first_fail, base + o_out, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, e->stream));
@@ -4470,103 +4497,38 @@ int swp_fit_pairs_volumes(swp_engine* e, const swp_task_desc* templates, uint32_
     return fit_pairs_impl(e, templates, n_templates, pairs, n_pairs, first_fail, out_att);
 }
 
-int swp_enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
-                uint8_t* out_reject) {
-    if (e && e->set) return ss::enforce(e, nodes, n_nodes, tasks, n_tasks, out_reject);
-    if (!e || (!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
+// swp_enforce and swp_enforce_generic: constraintenforcer.rejectNoncompliantTasks for the listed nodes. task_res_off == nullptr is
+// swp_enforce — no task holds an assignment, the sweep ends at line 184 of the reference. Otherwise the sweep's last third
+// (constraint_enforcer.go:186-200) runs too: the nodes none of whose tasks holds an assignment go to k_enforce, every other node to
+// one wave of k_enforce_generic (swp_enforce.hpp) with its list of available resources. out_reject is written only when the whole
+// call succeeds.
+static int enforce_impl(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks, const uint32_t* node_res_off,
+                        const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res, uint8_t* out_reject) {
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        if (nodes[i].node >= e->nodes.size() || !e->nodes[nodes[i].node].present) return e->fail(SWP_ENOTFOUND, "enforce: node %u is not in the nodeSet mirror", nodes[i].node);
+        if ((uint64_t)nodes[i].first_task + nodes[i].n_tasks > n_tasks) return e->fail(SWP_EINVAL, "enforce: node %u lists tasks beyond the task array", i);
+    }
     if (n_tasks == 0 || n_nodes == 0) {
         if (n_tasks) std::memset(out_reject, 0, n_tasks);
         return SWP_OK;
     }
-    (void)hipSetDevice(e->device);
-    for (uint32_t i = 0; i < n_nodes; ++i) {
-        if (nodes[i].node >= e->nodes.size() || !e->nodes[nodes[i].node].present) return e->fail(SWP_ENOTFOUND, "enforce: node %u is not in the nodeSet mirror", nodes[i].node);
-        if ((uint64_t)nodes[i].first_task + nodes[i].n_tasks > n_tasks) return e->fail(SWP_EINVAL, "enforce: node %u lists tasks beyond the task array", i);
-    }
-    // the constraint sets in play become classes exactly as for a scheduling batch (one pseudo task per enforce task)
-    uint32_t svc = 0;
-    {
-        static const char kDummy[] = "\0swp-enforce";
-        int rc = swp_intern(e, SWP_SPACE_SERVICE, kDummy, sizeof kDummy - 1, &svc);
-        if (rc) return rc;
-    }
-    std::vector<swp_task_desc> descs(n_tasks);
-    std::memset(descs.data(), 0, descs.size() * sizeof(swp_task_desc));
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-        descs[i].service = svc;
-        descs[i].constraint_set = tasks[i].constraint_set;
-    }
-    int rc = flush_nodes(e);
-    if (rc) return rc;
-    swp_batch b;
-    if ((rc = build_batch(e, descs.data(), n_tasks, &b, nullptr))) return rc;
-    if ((rc = flush_nodes(e))) return rc;
-    if ((rc = upload_batch(e, &b))) return rc;
-    if ((rc = run_classes(e, &b))) return rc;
-    const uint32_t Wn = n_words_of(e->n_nodes);
-    std::vector<EnfNode> en(n_nodes);
-    std::vector<EnfTask> et(n_tasks);
-    for (uint32_t i = 0; i < n_nodes; ++i) en[i] = EnfNode{nodes[i].node, nodes[i].first_task, nodes[i].n_tasks, 0u, nodes[i].cpu, nodes[i].mem};
-    for (uint32_t i = 0; i < n_tasks; ++i)
-        et[i] = EnfTask{tasks[i].cpu, tasks[i].mem, b.rt[i].cls_con, tasks[i].flags & SWP_ENF_RESERVATIONS, tasks[i].desired_state, tasks[i].state};
-    DevBuf d_en, d_et, d_out;
-    if ((rc = upload(e, d_en, en))) return rc;
-    if ((rc = upload(e, d_et, et))) return rc;
-    HIPCHECK(e, d_out.reserve(n_tasks));
-    hipStream_t st = e->stream;
-    HIPCHECK(e, hipMemsetAsync(d_out.p, 0, n_tasks, st));
-    hipLaunchKernelGGL(k_enforce, dim3((n_nodes + 255) / 256), dim3(256), 0, st, n_nodes, Wn, d_en.as<EnfNode>(), d_et.as<EnfTask>(),
-                       b.d_con.as<u64>(), d_out.as<unsigned char>());
-    HIPCHECK(e, hipGetLastError());
-    HIPCHECK(e, hipMemcpyAsync(out_reject, d_out.p, n_tasks, hipMemcpyDeviceToHost, st));
-    HIPCHECK(e, hipStreamSynchronize(st));
-    return SWP_OK;
-}
-
-// swp_enforce with the sweep's last third (constraint_enforcer.go:186-200): the nodes none of whose tasks holds an assignment go to
-// k_enforce as in swp_enforce, every other node to one wave of k_enforce_generic (swp_enforce.hpp) with its list of available resources.
-int swp_enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
-                        const uint32_t* node_res_off, const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res,
-                        uint8_t* out_reject) {
-    if (e && e->set) return ss::enforce_generic(e, nodes, n_nodes, tasks, n_tasks, node_res_off, node_res, task_res_off, task_res, out_reject);
-    if (!e || (!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
-    if (int rc = enforce_generic_check(e, (uint32_t)e->spaces[SWP_SPACE_GENERIC_KIND].strs.size(), n_nodes, n_tasks, node_res_off, node_res, task_res_off, task_res)) return rc;
-    for (uint32_t i = 0; i < n_nodes; ++i) {
-        if (nodes[i].node >= e->nodes.size() || !e->nodes[nodes[i].node].present) return e->fail(SWP_ENOTFOUND, "enforce: node %u is not in the nodeSet mirror", nodes[i].node);
-        if ((uint64_t)nodes[i].first_task + nodes[i].n_tasks > n_tasks) return e->fail(SWP_EINVAL, "enforce: node %u lists tasks beyond the task array", i);
-    }
     // the nodes with a task that holds an assignment, and whether one of their lists is longer than a wave
     std::vector<uint32_t> gen_src;
     bool long_list = false;
-    for (uint32_t i = 0; i < n_nodes; ++i) {
+    for (uint32_t i = 0; task_res_off && i < n_nodes; ++i) {
         const uint32_t t0 = nodes[i].first_task, t1 = t0 + nodes[i].n_tasks;
         if (t1 > t0 && task_res_off[t1] > task_res_off[t0]) {
             gen_src.push_back(i);
             long_list = long_list || node_res_off[i + 1] - node_res_off[i] > 64u;
         }
     }
-    if (gen_src.empty()) return swp_enforce(e, nodes, n_nodes, tasks, n_tasks, out_reject);
     (void)hipSetDevice(e->device);
-    // the constraint classes as in swp_enforce: one pseudo task per enforce task
-    uint32_t svc = 0;
-    {
-        static const char kDummy[] = "\0swp-enforce";
-        int rc = swp_intern(e, SWP_SPACE_SERVICE, kDummy, sizeof kDummy - 1, &svc);
-        if (rc) return rc;
-    }
-    std::vector<swp_task_desc> descs(n_tasks);
-    std::memset(descs.data(), 0, descs.size() * sizeof(swp_task_desc));
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-        descs[i].service = svc;
-        descs[i].constraint_set = tasks[i].constraint_set;
-    }
-    int rc = flush_nodes(e);
-    if (rc) return rc;
+    // the constraint sets in play become classes exactly as for a scheduling batch (one pseudo task per enforce task)
+    std::vector<uint32_t> sets(n_tasks);
+    for (uint32_t i = 0; i < n_tasks; ++i) sets[i] = tasks[i].constraint_set;
     swp_batch b;
-    if ((rc = build_batch(e, descs.data(), n_tasks, &b, nullptr))) return rc;
-    if ((rc = flush_nodes(e))) return rc;
-    if ((rc = upload_batch(e, &b))) return rc;
-    if ((rc = run_classes(e, &b))) return rc;
+    int rc = constraint_classes(e, sets.data(), n_tasks, &b);
+    if (rc) return rc;
     const uint32_t Wn = n_words_of(e->n_nodes);
     // the node records: the plain nodes first (k_enforce's share), then the generic ones in gen_src's order
     const uint32_t n_gen = (uint32_t)gen_src.size(), n_plain = n_nodes - n_gen;
@@ -4581,26 +4543,10 @@ int swp_enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n
     std::vector<EnfTask> et(n_tasks);
     for (uint32_t i = 0; i < n_tasks; ++i)
         et[i] = EnfTask{tasks[i].cpu, tasks[i].mem, b.rt[i].cls_con, tasks[i].flags & SWP_ENF_RESERVATIONS, tasks[i].desired_state, tasks[i].state};
-    static_assert(sizeof(swp_enforce_res) == sizeof(EnfRes), "swp_enforce_res is the device's record");
-    const size_t n_nres = node_res_off[n_nodes], n_tres = task_res_off[n_tasks];
     DevBuf d_en, d_et, d_out, d_src, d_noff, d_nres, d_work, d_toff, d_tres;
     if ((rc = upload(e, d_en, en))) return rc;
     if ((rc = upload(e, d_et, et))) return rc;
-    if ((rc = upload(e, d_src, gen_src))) return rc;
     hipStream_t st = e->stream;
-    auto put = [&](DevBuf& d, const void* src, size_t bytes) -> int {
-        HIPCHECK(e, d.reserve(std::max<size_t>(bytes, 16)));
-        if (bytes) HIPCHECK(e, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
-        return SWP_OK;
-    };
-    if ((rc = put(d_noff, node_res_off, ((size_t)n_nodes + 1) * 4))) return rc;
-    if ((rc = put(d_nres, node_res, n_nres * sizeof(EnfRes)))) return rc;
-    if ((rc = put(d_toff, task_res_off, ((size_t)n_tasks + 1) * 4))) return rc;
-    if ((rc = put(d_tres, task_res, n_tres * sizeof(EnfRes)))) return rc;
-    if (long_list) {   // the copy the waves of the long lists work on
-        HIPCHECK(e, d_work.reserve(n_nres * sizeof(EnfRes)));
-        HIPCHECK(e, hipMemcpyAsync(d_work.p, d_nres.p, n_nres * sizeof(EnfRes), hipMemcpyDeviceToDevice, st));
-    }
     HIPCHECK(e, d_out.reserve(n_tasks));
     HIPCHECK(e, hipMemsetAsync(d_out.p, 0, n_tasks, st));
     if (n_plain) {
@@ -4608,20 +4554,36 @@ int swp_enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n
                            d_out.as<unsigned char>());
         HIPCHECK(e, hipGetLastError());
     }
-    EnfGenArgs ga{};
-    ga.n_gen = n_gen;
-    ga.n_words = Wn;
-    ga.nodes = d_en.as<EnfNode>() + n_plain;
-    ga.src = d_src.as<u32>();
-    ga.tasks = d_et.as<EnfTask>();
-    ga.con = b.d_con.as<u64>();
-    ga.node_res_off = d_noff.as<u32>();
-    ga.node_res = d_nres.as<EnfRes>();
-    ga.work = long_list ? d_work.as<EnfRes>() : nullptr;
-    ga.task_res_off = d_toff.as<u32>();
-    ga.task_res = d_tres.as<EnfRes>();
-    ga.out = d_out.as<unsigned char>();
-    {
+    if (n_gen) {
+        static_assert(sizeof(swp_enforce_res) == sizeof(EnfRes), "swp_enforce_res is the device's record");
+        const size_t n_nres = node_res_off[n_nodes], n_tres = task_res_off[n_tasks];
+        if ((rc = upload(e, d_src, gen_src))) return rc;
+        auto put = [&](DevBuf& d, const void* src, size_t bytes) -> int {
+            HIPCHECK(e, d.reserve(std::max<size_t>(bytes, 16)));
+            if (bytes) HIPCHECK(e, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
+            return SWP_OK;
+        };
+        if ((rc = put(d_noff, node_res_off, ((size_t)n_nodes + 1) * 4))) return rc;
+        if ((rc = put(d_nres, node_res, n_nres * sizeof(EnfRes)))) return rc;
+        if ((rc = put(d_toff, task_res_off, ((size_t)n_tasks + 1) * 4))) return rc;
+        if ((rc = put(d_tres, task_res, n_tres * sizeof(EnfRes)))) return rc;
+        if (long_list) {   // the copy the waves of the long lists work on
+            HIPCHECK(e, d_work.reserve(n_nres * sizeof(EnfRes)));
+            HIPCHECK(e, hipMemcpyAsync(d_work.p, d_nres.p, n_nres * sizeof(EnfRes), hipMemcpyDeviceToDevice, st));
+        }
+        EnfGenArgs ga{};
+        ga.n_gen = n_gen;
+        ga.n_words = Wn;
+        ga.nodes = d_en.as<EnfNode>() + n_plain;
+        ga.src = d_src.as<u32>();
+        ga.tasks = d_et.as<EnfTask>();
+        ga.con = b.d_con.as<u64>();
+        ga.node_res_off = d_noff.as<u32>();
+        ga.node_res = d_nres.as<EnfRes>();
+        ga.work = long_list ? d_work.as<EnfRes>() : nullptr;
+        ga.task_res_off = d_toff.as<u32>();
+        ga.task_res = d_tres.as<EnfRes>();
+        ga.out = d_out.as<unsigned char>();
         hipError_t r = launch_enforce_generic(ga, st);
         if (r != hipSuccess) return e->fail(SWP_EHIP, "k_enforce_generic launch: %s", hipGetErrorString(r));
     }
@@ -4630,6 +4592,23 @@ int swp_enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n
     HIPCHECK(e, hipStreamSynchronize(st));
     std::memcpy(out_reject, rej.data(), n_tasks);
     return SWP_OK;
+}
+
+int swp_enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
+                uint8_t* out_reject) {
+    if (e && e->set) return ss::enforce_generic(e, nodes, n_nodes, tasks, n_tasks, nullptr, nullptr, nullptr, nullptr, out_reject, true);
+    if (!e || (!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
+    if (n_tasks == 0) n_nodes = 0;   // (nothing to judge: this entry has never looked at the node list of such a call)
+    return enforce_impl(e, nodes, n_nodes, tasks, n_tasks, nullptr, nullptr, nullptr, nullptr, out_reject);
+}
+
+int swp_enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks,
+                        const uint32_t* node_res_off, const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res,
+                        uint8_t* out_reject) {
+    if (e && e->set) return ss::enforce_generic(e, nodes, n_nodes, tasks, n_tasks, node_res_off, node_res, task_res_off, task_res, out_reject, false);
+    if (!e || (!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
+    if (int rc = enforce_generic_check(e, (uint32_t)e->spaces[SWP_SPACE_GENERIC_KIND].strs.size(), n_nodes, n_tasks, node_res_off, node_res, task_res_off, task_res)) return rc;
+    return enforce_impl(e, nodes, n_nodes, tasks, n_tasks, node_res_off, node_res, task_res_off, task_res, out_reject);
 }
 
 int swp_node_matches(swp_engine* e, const uint32_t* constraint_sets, uint32_t n_sets, uint64_t* out_bitmaps, uint32_t n_words) {
@@ -4642,22 +4621,8 @@ int swp_node_matches(swp_engine* e, const uint32_t* constraint_sets, uint32_t n_
     const uint32_t Wn = n_words_of(e->n_nodes);
     if (n_words != Wn) return e->fail(SWP_EINVAL, "node_matches: caller passes %u words per row, the nodeSet has %u", n_words, Wn);
     if (e->n_nodes == 0) return SWP_OK;
-    uint32_t svc = 0;
-    {
-        static const char kDummy[] = "\0swp-enforce";
-        if ((rc = swp_intern(e, SWP_SPACE_SERVICE, kDummy, sizeof kDummy - 1, &svc))) return rc;
-    }
-    std::vector<swp_task_desc> descs(n_sets);
-    std::memset(descs.data(), 0, descs.size() * sizeof(swp_task_desc));
-    for (uint32_t i = 0; i < n_sets; ++i) {
-        descs[i].service = svc;
-        descs[i].constraint_set = constraint_sets[i];
-    }
     swp_batch b;
-    if ((rc = build_batch(e, descs.data(), n_sets, &b, nullptr))) return rc;
-    if ((rc = flush_nodes(e))) return rc;
-    if ((rc = upload_batch(e, &b))) return rc;
-    if ((rc = run_classes(e, &b))) return rc;
+    if ((rc = constraint_classes(e, constraint_sets, n_sets, &b))) return rc;
     hipStream_t st = e->stream;
     for (uint32_t i = 0; i < n_sets; ++i) {
         const uint32_t cls = b.rt[i].cls_con;

@@ -24,8 +24,11 @@ struct VolTopoArgs;
 struct VolChooseArgs;
 hipError_t launch_vol_topology(const VolTopoArgs& a, hipStream_t s);
 hipError_t launch_vol_choose(const VolChooseArgs& a, hipStream_t s);
+// the preassigned pair pass (swp_fitpairs.hpp, built in swp_resolve6.hip): a call without a mount template, and one with
+struct FitArgs;
 struct FitVolArgs;
-hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s);   // k_fit_pairs_vol (swp_fitpairs.hpp)
+hipError_t launch_fit_pairs(const FitArgs& a, hipStream_t s);          // k_fit_pairs
+hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s);   // k_fit_pairs_vol
 
 // the enforcer sweep's nodes with a generic task (swp_enforce.hpp, built in swp_resolve6.hip): one wave per node
 struct EnfGenArgs;

@@ -74,7 +74,12 @@ hipError_t launch_vol_choose(const VolChooseArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the preassigned pair pass of a call with cluster mounts (swp_fitpairs.hpp): one thread per node segment
+// the preassigned pair pass (swp_fitpairs.hpp), without and with cluster mounts: one thread per node segment
+hipError_t launch_fit_pairs(const FitArgs& a, hipStream_t s) {
+    if (a.n_seg == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit_pairs, dim3((a.n_seg + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 hipError_t launch_fit_pairs_vol(const FitVolArgs& a, hipStream_t s) {
     if (a.f.n_seg == 0) return hipSuccess;
     hipLaunchKernelGGL(k_fit_pairs_vol, dim3((a.f.n_seg + 255) / 256), dim3(256), 0, s, a);

@@ -97,10 +97,9 @@ int create(const swp_config* cfg, const int32_t* devices, uint32_t n_shards, uin
     e->device = S->sh[0]->device;
     e->set = S.release();
     {   // the service the enforcer's pseudo tasks carry (swp_enforce interns it on first use: here every shard has it from the start)
-        static const char kDummy[] = "\0swp-enforce";
         for (swp_engine* c : e->set->all) {
             uint32_t id = 0;
-            (void)swp_intern(c, SWP_SPACE_SERVICE, kDummy, sizeof kDummy - 1, &id);
+            (void)intern_enforce_service(c, &id);
         }
     }
     *out = e.release();
@@ -613,18 +612,8 @@ int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_template
     if ((!templates && n_templates) || (!pairs && n_pairs) || (!first_fail && n_pairs)) return SWP_EINVAL;
     if (S.broken) return broken_error(e);
     if (n_pairs == 0) return SWP_OK;
-    const swp_engine* c0 = S.sh[0];   // (predicate sets and ids are replicated: shard 0 speaks for all)
-    for (uint32_t t = 0; t < n_templates; ++t) {
-        const swp_task_desc& d = templates[t];
-        if (!out_att && (d.flags >> SWP_TASK_MOUNTS_SHIFT)) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has cluster mounts (swp_check_node + swp_choose_volumes)", t);
-        if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) >= c0->mount_sets.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown mount set", t);
-        if (d.spread_set) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has spread preferences", t);
-        if (d.cpu < 0 || d.mem < 0) return e->fail(SWP_EUNSUPPORTED, "fit_pairs: template %u has a negative resource reservation", t);
-        if (d.service >= c0->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "fit_pairs: template %u: unknown service id %u", t, d.service);
-        if (d.constraint_set >= c0->con_sets.size() || d.platform_set >= c0->plat_sets.size() || d.plugin_set >= c0->plug_sets.size() ||
-            d.port_set >= c0->port_sets.size() || d.generic_set >= c0->gen_sets.size())
-            return e->fail(SWP_EINVAL, "fit_pairs: template %u references an unknown predicate set", t);
-    }
+    bool any_mounts = false;
+    if (int rc = fit_templates_check(e, S.sh[0], templates, n_templates, out_att != nullptr, &any_mounts)) return rc;   // (predicate sets and ids are replicated: shard 0 speaks for all)
     std::vector<std::vector<swp_fit_pair>> per(S.sh.size());
     std::vector<std::vector<uint32_t>> src(S.sh.size());
     for (uint32_t i = 0; i < n_pairs; ++i) {
@@ -652,44 +641,16 @@ int fit_pairs(swp_engine* e, const swp_task_desc* templates, uint32_t n_template
     return SWP_OK;
 }
 
-int enforce(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks, uint8_t* out_reject) {
-    ShardSet& S = *e->set;
-    if ((!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
-    if (n_tasks) std::memset(out_reject, 0, n_tasks);
-    struct Part { std::vector<swp_enforce_node> nodes; std::vector<swp_enforce_task> tasks; std::vector<uint32_t> src; };
-    std::vector<Part> per(S.sh.size());
-    for (uint32_t i = 0; i < n_nodes; ++i) {
-        uint32_t g = 0, l = 0;
-        if (!locate(S, nodes[i].node, &g, &l)) return e->fail(SWP_ENOTFOUND, "enforce: node %u is not in the nodeSet mirror", nodes[i].node);
-        if ((uint64_t)nodes[i].first_task + nodes[i].n_tasks > n_tasks) return e->fail(SWP_EINVAL, "enforce: node %u lists tasks beyond the task array", i);
-        Part& P = per[g];
-        swp_enforce_node q = nodes[i];
-        q.node = l;
-        q.first_task = (uint32_t)P.tasks.size();
-        for (uint32_t k = 0; k < nodes[i].n_tasks; ++k) {
-            P.tasks.push_back(tasks[nodes[i].first_task + k]);
-            P.src.push_back(nodes[i].first_task + k);
-        }
-        P.nodes.push_back(q);
-    }
-    for (size_t g = 0; g < per.size(); ++g) {
-        Part& P = per[g];
-        if (P.tasks.empty()) continue;
-        std::vector<uint8_t> rej(P.tasks.size(), 0);
-        if (int rc = swp_enforce(S.sh[g], P.nodes.data(), (uint32_t)P.nodes.size(), P.tasks.data(), (uint32_t)P.tasks.size(), rej.data())) return take_error(e, S.sh[g], rc);
-        for (size_t k = 0; k < rej.size(); ++k) out_reject[P.src[k]] = rej[k];
-    }
-    return SWP_OK;
-}
-
-// swp_enforce_generic: split by the owner of each node as enforce above; every part carries its slices of the four arrays (offsets
-// rebased). Everything a shard would refuse is refused here first, and the verdicts reach out_reject only when every shard has answered.
+// swp_enforce (plain: the four resource arrays are null — no task holds an assignment, every slice is empty) and swp_enforce_generic: split by the
+// owner of each node; every part carries its slices of the four arrays (offsets rebased). Everything a shard would refuse is refused here first, and the
+// verdicts reach out_reject only when every shard has answered.
 int enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nodes, const swp_enforce_task* tasks, uint32_t n_tasks, const uint32_t* node_res_off,
-                    const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res, uint8_t* out_reject) {
+                    const swp_enforce_res* node_res, const uint32_t* task_res_off, const swp_enforce_res* task_res, uint8_t* out_reject, bool plain) {
     ShardSet& S = *e->set;
     if ((!nodes && n_nodes) || (!tasks && n_tasks) || (!out_reject && n_tasks)) return SWP_EINVAL;
     if (S.broken) return broken_error(e);
-    if (int rc = enforce_generic_check(e, (uint32_t)S.sh[0]->spaces[SWP_SPACE_GENERIC_KIND].strs.size(), n_nodes, n_tasks, node_res_off, node_res, task_res_off, task_res)) return rc;
+    if (!plain)
+        if (int rc = enforce_generic_check(e, (uint32_t)S.sh[0]->spaces[SWP_SPACE_GENERIC_KIND].strs.size(), n_nodes, n_tasks, node_res_off, node_res, task_res_off, task_res)) return rc;
     struct Part {
         std::vector<swp_enforce_node> nodes;
         std::vector<swp_enforce_task> tasks;
@@ -710,11 +671,11 @@ int enforce_generic(swp_engine* e, const swp_enforce_node* nodes, uint32_t n_nod
             const uint32_t t = nodes[i].first_task + k;
             P.tasks.push_back(tasks[t]);
             P.src.push_back(t);
-            P.tres.insert(P.tres.end(), task_res + task_res_off[t], task_res + task_res_off[t + 1]);
+            if (!plain) P.tres.insert(P.tres.end(), task_res + task_res_off[t], task_res + task_res_off[t + 1]);
             P.toff.push_back((uint32_t)P.tres.size());
         }
         P.nodes.push_back(q);
-        P.nres.insert(P.nres.end(), node_res + node_res_off[i], node_res + node_res_off[i + 1]);
+        if (!plain) P.nres.insert(P.nres.end(), node_res + node_res_off[i], node_res + node_res_off[i + 1]);
         P.noff.push_back((uint32_t)P.nres.size());
     }
     std::vector<uint8_t> all(n_tasks, 0), rej;

@@ -1,5 +1,5 @@
 // emu_volumes.cpp — runs the CSI volume code of swarmkit_amd/csrc/swp_volumes.hpp (vol_check, vol_for_mount, vol_filter_word, vol_choose,
-// vol_reserve, k_vol_choose, k_vol_topology) and the preassigned pair pass with cluster mounts (swp_fitpairs.hpp: k_fit_pairs_vol) on CPU
+// vol_reserve, k_vol_choose, k_vol_topology) and the preassigned pair pass (swp_fitpairs.hpp: k_fit_pairs_vol, k_fit_pairs) on CPU
 // fibers (wv_emu.hpp) against the volume model of emu_model.hpp — a per-node, per-mount restatement of the reference's VolumeSet that keeps
 // usage as the set of (task, node, read-only) and derives the device's numbers from it. TEST INFRASTRUCTURE (tests/test_emu_volumes.py).
 //
@@ -7,6 +7,7 @@
 //   emu_volumes functions <seed> <N>              k_vol_choose per (mount set, node), vol_filter_word per (set, word), vol_reserve over placements
 //   emu_volumes topology <seed> <N>               k_vol_topology over its grid, two launches (vol0 > 0 for the second)
 //   emu_volumes fitpairs <seed> <n_seg> <hot> [z] k_fit_pairs_vol against a sequential loop over the pairs; hot: pairs of segment 0; z: no volumes
+//   emu_volumes fitpairs <seed> <n_seg> <hot> p   plain: no template has a mount set, the kernel is k_fit_pairs; no attachment row may be touched
 // Every mode prints "reach ..." lines: what the MODEL's run came across (the Python test asserts on them), then "-> OK" or the difference.
 #include "wv_emu.hpp"
 
@@ -287,7 +288,7 @@ static int topology(u32 seed, u32 N) {
 }
 
 // ---- fitpairs ----
-static int fitpairs(u32 seed, u32 n_seg, u32 hot, bool no_vol) {
+static int fitpairs(u32 seed, u32 n_seg, u32 hot, bool no_vol, bool plain) {
     const u32 N = n_seg + n_seg / 3 + 70, Wn = (N + 63) / 64;
     VolProblem vp = make_volumes(seed, N, 12, 30);
     VolTables tb = vol_tables(vp);
@@ -347,7 +348,7 @@ static int fitpairs(u32 seed, u32 n_seg, u32 hot, bool no_vol) {
         }
         if (rnd(4) == 0) { f.rt.flags |= RT_MAXREP; f.rt.maxrep = 1 + rnd(3); }
         if (rnd(8) == 0) f.rt.flags |= RT_UNCOUNTED;
-        if (rnd(2)) f.mset = 1 + rnd(n_sets - 1);
+        if (rnd(2) && !plain) f.mset = 1 + rnd(n_sets - 1);   // (plain: the model's VolumesFilter and choose lines are inert)
     }
     gkind.push_back(0);
     gval.push_back(0);
@@ -460,7 +461,12 @@ static int fitpairs(u32 seed, u32 n_seg, u32 hot, bool no_vol) {
     av.f.out = out.data();
     if (!no_vol) av.vol = tb.view();   // (no volume exists: every pointer null)
     av.att = att.data();
-    grid2((n_seg + 255) / 256, 1, 256, [av]() { k_fit_pairs_vol(av); });
+    if (plain) {   // k_fit_pairs gets FitArgs alone; every attachment row must stay as the caller left it
+        grid2((n_seg + 255) / 256, 1, 256, [av]() { k_fit_pairs(av.f); });
+        m_att.assign(m_att.size(), 0xABABABABu);
+    } else {
+        grid2((n_seg + 255) / 256, 1, 256, [av]() { k_fit_pairs_vol(av); });
+    }
 
     bool ok = same("out", out, m_out, NP) && same("att", att, m_att, att.size()) && same("cpu", cpu, m_cpu, N) && same("mem", mem, m_mem, N) && same("total", total, m_total, N) &&
               same("gcnt", gcnt, m_gcnt, gcnt.size()) && same("svc_cnt", svc_cnt, m_svc, svc_cnt.size()) && same("port_taken", port_taken, m_port, port_taken.size());
@@ -470,7 +476,7 @@ static int fitpairs(u32 seed, u32 n_seg, u32 hot, bool no_vol) {
     for (u32 f = 0; f < 9; ++f) fprintf(stderr, " ff%u=%llu", f, (unsigned long long)hist[f + 1]);
     fprintf(stderr, " clamped=%llu drained_segments=%llu uncounted=%llu port_of_a_pair_in_front=%llu maxrep_inside=%llu\n", (unsigned long long)clamped, (unsigned long long)drained_seg,
             (unsigned long long)uncounted, (unsigned long long)shared_port, (unsigned long long)maxrep_inside);
-    fprintf(stderr, "fitpairs seed %u segments %u (hot %u) nodes %u pairs %u volumes %s -> %s\n", seed, n_seg, hot, N, NP, no_vol ? "none" : "yes", ok ? "OK" : "FAIL");
+    fprintf(stderr, "fitpairs seed %u segments %u (hot %u) nodes %u pairs %u volumes %s -> %s\n", seed, n_seg, hot, N, NP, plain ? "unused" : no_vol ? "none" : "yes", ok ? "OK" : "FAIL");
     return ok ? 0 : 1;
 }
 
@@ -479,7 +485,7 @@ int main(int argc, char** argv) {
     if (mode == "selftest") return selftest();
     if (mode == "functions" && argc >= 4) return functions(atoi(argv[2]), atoi(argv[3]));
     if (mode == "topology" && argc >= 4) return topology(atoi(argv[2]), atoi(argv[3]));
-    if (mode == "fitpairs" && argc >= 5) return fitpairs(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 && argv[5][0] == 'z');
-    fprintf(stderr, "usage: %s selftest | functions seed N | topology seed N | fitpairs seed n_seg hot [z]\n", argv[0]);
+    if (mode == "fitpairs" && argc >= 5) return fitpairs(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 && argv[5][0] == 'z', argc > 5 && argv[5][0] == 'p');
+    fprintf(stderr, "usage: %s selftest | functions seed N | topology seed N | fitpairs seed n_seg hot [z|p]\n", argv[0]);
     return 2;
 }

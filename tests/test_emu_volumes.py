@@ -1,5 +1,6 @@
 """CPU: the CSI volume code (swarmkit_amd/csrc/swp_volumes.hpp: vol_check, vol_for_mount, vol_filter_word, vol_choose, vol_reserve,
-k_vol_choose, k_vol_topology) and the preassigned pair pass with cluster mounts (swp_fitpairs.hpp: k_fit_pairs_vol) run on fibers
+k_vol_choose, k_vol_topology) and the preassigned pair pass (swp_fitpairs.hpp: k_fit_pairs_vol, and k_fit_pairs for calls without
+mounts) run on fibers
 (tests/emu/wv_emu.hpp) against the volume model of tests/emu/emu_model.hpp: a per-node, per-mount restatement of the reference's
 VolumeSet that keeps usage as (task, node, read-only) and derives the device's {tasks, writers, pin} from it. The model itself is
 pinned by the known answers of tests/kat_volumes.py (selftest). No GPU involved; the GPU parity is tests/test_engine_volumes.py and
@@ -132,3 +133,24 @@ def test_fit_pairs_reach(emu_bin):
         assert any(s[k] > 0 for s in shapes), k
     novol = shapes[[c[3] for c in FITPAIRS].index("z")]
     assert novol["ff7"] > 0 and novol["ff8"] == 0   # no volume exists: VolumesFilter fails every mount template
+
+
+# the plain kernel over the same segment counts and hot sizes, and 257 segments of ordinary size: the second workgroup holds one live thread
+FITPAIRS_PLAIN = [(c[0], c[1], c[2], "p") for c in FITPAIRS if c[3] == ""] + [(8, 257, 0, "p")]
+
+
+@pytest.mark.parametrize("case", FITPAIRS_PLAIN, ids=lambda c: "seed%d-seg%d-hot%d%s" % c)
+def test_fit_pairs_without_mounts(emu_bin, case):
+    """k_fit_pairs — the same segment walk instantiated without mounts, FitArgs alone — against the same sequential loop (no template has
+    a mount set: its VolumesFilter and choose lines do nothing): verdicts, node rows, generic counts, service counts and host ports; no
+    attachment row is touched."""
+    run_ok(emu_bin, "fitpairs", *case)
+
+
+def test_fit_pairs_without_mounts_reach(emu_bin):
+    shapes = [reach(run_ok(emu_bin, "fitpairs", *c), "fitpairs shapes") for c in FITPAIRS_PLAIN]
+    for k in ["ff_pass"] + ["ff%d" % f for f in range(7)]:   # every first-fail value -1, 0 .. 6 in at least one case
+        assert any(s[k] > 0 for s in shapes), k
+    assert all(s["ff7"] == 0 and s["ff8"] == 0 for s in shapes)
+    for k in ["clamped", "drained_segments", "uncounted", "port_of_a_pair_in_front", "maxrep_inside"]:
+        assert any(s[k] > 0 for s in shapes), k

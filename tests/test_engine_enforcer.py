@@ -3,13 +3,14 @@ engine, and seeded random clusters (labels, roles, constraints from current serv
 import os
 import random
 
+import numpy as np
 import pytest
 
 import pyhost
 
 import orc
 import test_oracle_enforcer as kat
-from swarmkit_amd import host as swhost
+from swarmkit_amd import abi, host as swhost
 
 pytestmark = pytest.mark.gpu
 
@@ -156,3 +157,27 @@ def test_node_matches_matrix_equals_per_pair_oracle():
         assert parsed is not None
         row = s2.e.node_matches([s2.constraint_set(cons)])
         assert bool(int(row[0, 0]) & 1) == want, (cons, node)
+
+
+@pytest.mark.parametrize("shards", [0, 2])
+def test_a_refused_call_leaves_the_callers_buffer_untouched(shards):
+    """swp_enforce answers into out_reject only when the whole call succeeds, on one engine and on a shard set alike: a node that is
+    not in the mirror refuses the call, and a buffer filled with 0xAB is still that. 130 nodes: three bitmap words, the last one partial;
+    one task on a node of each word."""
+    s = swhost.HostScheduler(shards=2, nodes_per_shard=70) if shards else swhost.HostScheduler()
+    for i in range(130):
+        s.create_node({"ID": "n%03d" % i, "Status": {"State": orc.READY}, "Spec": {"Availability": 0},
+                       "Description": {"Hostname": "h%d" % i, "Resources": {"NanoCPUs": 10**9, "MemoryBytes": 1 << 30}}})
+    nodes = np.zeros(3, dtype=abi.ENF_NODE_DTYPE)
+    tasks = np.zeros(3, dtype=abi.ENF_TASK_DTYPE)
+    for k, n in enumerate([0, 64, 129]):
+        nodes[k] = (n, k, 1, 0, 10**9, 1 << 30)
+        tasks[k] = (2 * 10**9 if k == 1 else 10**8, 1 << 20, 0, abi.ENF_RESERVATIONS, orc.RUNNING, orc.RUNNING)
+    out = np.full(3, 0xAB, dtype=np.uint8)
+    absent = nodes.copy()
+    absent["node"][1] = 12345
+    with pytest.raises(abi.SwpError) as err:
+        s.e.enforce(absent, tasks, out=out)
+    assert err.value.code == abi.SWP_ENOTFOUND
+    assert list(out) == [0xAB] * 3
+    assert list(s.e.enforce(nodes, tasks, out=out)) == [0, 1, 0]   # ... and the same buffer takes the verdicts of a call that succeeds

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Developer aid: per-kernel register use and instruction histogram from `make -C swarmkit_amd/csrc asm`."""
+"""Developer aid: per-kernel register use and instruction histogram from `make -C swarmkit_amd/csrc asm [ASM_TU=swp_resolve6]` (the pair
+kernels k_fit_pairs / k_fit_pairs_vol are built in swp_resolve6.hip, k_check_pair and k_explain in swp_engine.hip)."""
+import glob
 import re
 import sys
 from collections import Counter
@@ -16,8 +18,8 @@ for b in re.split(r'Function Name: ', txt)[1:]:
         return m.group(1) if m else '?'
     print(name[:56].ljust(56), 'VGPR', g('VGPRs'), 'SGPR', g('TotalSGPRs'), 'scratch', g(r'ScratchSize \[bytes/lane\]'), 'occ', g(r'Occupancy \[waves/SIMD\]'),
           'spillV', g('VGPRs Spill'))
-s = open(d + 'swp_engine-hip-amdgcn-amd-amdhsa-gfx950.s').read()
 sym = sys.argv[2] if len(sys.argv) > 2 else '_ZN6swpdev9k_explainENS_11ExplainArgsE'
+s = next(t for t in (open(f).read() for f in sorted(glob.glob(d + '*-hip-amdgcn-amd-amdhsa-gfx950.s'))) if sym + ':' in t)   # (the translation unit last built there)
 i = s.index(sym + ':')
 j = s.index('.end_amdhsa_kernel', i) if '.end_amdhsa_kernel' in s[i:] else len(s)
 lines = s[i:j].split('\n')
