@@ -31,6 +31,7 @@
 #include "swp_launch.hpp"
 #include "swp_resolve6.hpp"
 #include "swp_resolve7.hpp"
+#include "swp_rounds.hpp"
 #include "swp_scan.hpp"
 #include "swp_shard.hpp"
 #include "swp_waterfill.hpp"
@@ -1799,6 +1800,39 @@ int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_row
     return SWP_OK;
 }
 
+// k_waterfill's argument record for a run of `count` identical tasks from j0 (b->d_wf holds 3 x n_nodes words: the caller reserved it)
+WaterArgs water_args_for(swp_engine* e, swp_batch* b, uint32_t j0, uint32_t count) {
+    const uint32_t N = e->n_nodes, Wn = n_words_of(N);
+    WaterArgs wa{};
+    wa.n_nodes = N;
+    wa.n_words = Wn;
+    wa.xs = Wn;
+    wa.j0 = j0;
+    wa.count = count;
+    wa.rt = b->d_rt.as<RTask>();
+    wa.sc = b->d_sc.as<u64>();
+    wa.cpu = e->d_cpu.as<long long>();
+    wa.mem = e->d_mem.as<long long>();
+    wa.total = e->d_total.as<uint32_t>();
+    wa.X = b->d_X.as<u64>();
+    wa.list_node = b->d_list_node.as<uint32_t>();
+    wa.list_svc = b->d_list_svc.as<uint32_t>();
+    wa.list_fail = b->d_list_fail.as<uint32_t>();
+    wa.list_off = b->d_list_off.as<uint32_t>();
+    wa.out_node = b->d_out.as<int32_t>();
+    wa.log_node = b->d_log_node.as<uint32_t>();
+    wa.log_task = b->d_log_task.as<uint32_t>();
+    wa.log_prev = b->d_log_prev.as<int32_t>();
+    wa.last = b->d_last.as<int32_t>();
+    wa.inf_task = b->d_inf_task.as<uint32_t>();
+    wa.inf_pos = b->d_inf_pos.as<uint32_t>();
+    wa.ctl = b->d_ctl.as<Ctl>();
+    wa.ps = b->d_wf.as<uint32_t>();
+    wa.cap = wa.ps + N;
+    wa.ent = wa.cap + N;
+    return wa;
+}
+
 int batch_run_impl(swp_engine* e, swp_batch* b);
 // Every failure exit of the device pass leaves the device node rows (cpu / mem / total) possibly half-updated — the resolvers commit
 // while they run — so the untouched host mirror is uploaded again before the next device call (as swp_schedule_groups does).
@@ -1823,23 +1857,15 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
     if (rc) return rc;
     if (prof) HIPCHECK(e, hipEventRecord(e->ev[1], st));
 
-    const size_t lds_budget = 160 * 1024 - 512;
     // k_resolve6, the BLOCK resolver: lists built by the whole chip from bitmap rows in global memory, matched by one wave. Needs the
-    // demand classes and two candidate buffers of the propose kernel in LDS (≈ 650k nodes). Test / debugging knobs, read once per
-    // batch: SWP_R6_BLOCK sets the tasks per round, SWP_DBG bit 16 switches the in-kernel section timers on.
-    const char* env_dbg = getenv("SWP_DBG");
-    const uint32_t dbg_bits = env_dbg ? (uint32_t)atoi(env_dbg) : 0u;
-    const char* env_blk = getenv("SWP_R6_BLOCK");
-    // (without the knob: as many 64-task groups as the commit kernel's LDS holds next to the TK row, at most R6_BLOCK_DEFAULT_CAP tasks)
-    uint32_t r6_block = std::min<uint32_t>(r6_block_max(), std::max<uint32_t>(1u, env_blk ? (uint32_t)atoi(env_blk) : R6_BLOCK_DEFAULT_CAP));
-    // demand-class rows patched by every commit while the batch has few distinct reservations; rows per task of the block, rebuilt
-    // every round from the exact residuals, when it has many (a commit would cross too many thresholds) — no limit then
-    const char* env_tr = getenv("SWP_R6_TASKROWS");
-    const bool r6_task_rows = env_tr ? atoi(env_tr) != 0 : (!b->classes_ok || b->n_dc + b->n_dm > 128);
+    // demand classes and two candidate buffers of the propose kernel in LDS (≈ 650k nodes). Knobs, row mode and block: swp_rounds.hpp
+    // (without SWP_R6_BLOCK: as many 64-task groups as the commit kernel's LDS holds next to the TK row, at most R6_BLOCK_DEFAULT_CAP tasks).
+    const R6Knobs knobs = r6_knobs(r6_block_max(), R6_BLOCK_DEFAULT_CAP);
+    const uint32_t dbg_bits = knobs.dbg;
+    const bool r6_task_rows = swpdev::r6_task_rows(knobs, b->classes_ok, b->n_dc + b->n_dm);
     const uint32_t r6_nrr = r6_task_rows ? 0u : b->n_dc + b->n_dm;
-    // (the commit kernel stages the block's lists in LDS next to the TK row: a very large node set gets a smaller block)
-    while (r6_block > 64 && r6_commit_lds_size(Wn, r6_block, r6_nrr) > lds_budget) r6_block = (r6_block - 1u) / 64u * 64u;
-    const bool r6_ok = r6_propose_lds_size(Wn) <= lds_budget && r6_commit_lds_size(Wn, r6_block, r6_nrr) <= lds_budget && Wn <= 32768u;   // (half-word indices of 16 bits in the commit kernel's LDS)
+    const uint32_t r6_block = r6_fit_block(knobs.block_cap, [&](uint32_t bl) { return r6_commit_lds_size(Wn, bl, r6_nrr); });
+    const bool r6_ok = r6_propose_lds_size(Wn) <= R6_LDS_BUDGET && r6_commit_lds_size(Wn, r6_block, r6_nrr) <= R6_LDS_BUDGET && Wn <= 32768u;   // (half-word indices of 16 bits in the commit kernel's LDS)
     if (!r6_ok) return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", N);
     uint32_t wi = 0;   // resolver stretches launched so far (profiling slots)
     uint64_t r6_rounds = 0;
@@ -1865,8 +1891,9 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
         HIPCHECK(e, hipMemcpyAsync(b->d_blk6.p, &hb, sizeof hb, hipMemcpyHostToDevice, st));
         hipError_t r = launch_r6_build(ra, st);
         if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 build launch: %s", hipGetErrorString(r));
-        uint32_t pos = start, chunk = std::min<uint32_t>(16u, (end - start + 255u) / 256u + 1u);   // a short stretch does not pay for empty rounds
-        uint32_t rounds_seen = 0, scan_len = 2048, scanned = 0, skipped_seen = 0;
+        RoundPace pace(end - start, r6_block, knobs.block_forced, start);
+        uint32_t& pos = pace.pos;
+        uint32_t scan_len = 2048, scanned = 0, skipped_seen = 0;
         bool after_scan = false;   // the rounds since the last scan stretch: four of them say whether the tasks still have no plain candidates
         // The compact index (swp_resolve6.hpp, R6Args.compact): one more small launch per round, worth it when the level the tasks aim at is a
         // sparse set of nodes (re-placements after a drain): the matcher then stops at an emptied half-word every few tasks and the rounds are
@@ -1875,7 +1902,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
         // one ended if the index was in use then.
         // SWP_R6_COMPACT=0 never, 1 from the first round on (tests, A/B runs).
         const char* env_cpt = getenv("SWP_R6_COMPACT");
-        const bool cpt_ok = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, r6_block, r6_nrr, true) <= lds_budget && b->csi_set.empty() && !(env_cpt && atoi(env_cpt) == 0);   // (no smaller blocks for it)
+        const bool cpt_ok = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, r6_block, r6_nrr, true) <= R6_LDS_BUDGET && b->csi_set.empty() && !(env_cpt && atoi(env_cpt) == 0);   // (no smaller blocks for it)
         bool cpt = cpt_ok && ((env_cpt && atoi(env_cpt) != 0) || e->r6_compact_hint);
         // (the index of the NEXT round built at the end of k_r6_commit_c instead of by a launch of its own: SWP_R6_COMPACT_FUSED=0 for A/B runs)
         const char* env_cf = getenv("SWP_R6_COMPACT_FUSED");
@@ -1893,7 +1920,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
         const bool scan_fast = scan_ok && ra.n_rg == 0 && ra.csi_of == nullptr && scan_batched_fits(N, b->n_svc, b->n_sc);
         while (pos < end) {
             ra.compact = cpt ? (cpt_fused ? 2u : 1u) : 0u;
-            r = launch_r6_rounds(ra, chunk, st, e->device);
+            r = launch_r6_rounds(ra, pace.chunk, st, e->device);
             if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 round launch: %s", hipGetErrorString(r));
             HIPCHECK(e, hipMemcpyAsync(&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
             HIPCHECK(e, hipStreamSynchronize(st));
@@ -1903,10 +1930,8 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
             // The rounds of this chunk decided only a handful of tasks each: the tasks here have no plain candidates (their services run on
             // every node that could take them) and a round ends behind the first of them. The scan resolver decides such a stretch one task
             // after the other at ~1 us each (swp_scan.hpp); afterwards the bitmaps are rebuilt and the rounds are tried again.
-            const uint32_t used = hb.rounds - rounds_seen;   // rounds that found work
-            const double recent = (double)(hb.pos - pos) / (double)std::max<uint32_t>(used, 1);
-            rounds_seen = hb.rounds;
-            pos = hb.pos;
+            const uint32_t used = hb.rounds - pace.rounds_seen;   // rounds that found work
+            const double recent = pace.observe(hb.pos, hb.rounds);
             if (dbg_bits & 32) fprintf(stderr, "[swp] chunk: %u rounds, %.1f tasks each, at %u of %u | block %u compact %u csize %u clevel %u base %u maxrel %u\n", used, recent, pos, end, ra.block, ra.compact, hb.csize, hb.clevel, hb.base, hb.maxrel);
             {
                 const uint32_t exh = hb.cut_exhausted - exh_seen, cr = hb.crounds - crounds_seen, stops = hb.reseats - stops_seen;
@@ -1954,7 +1979,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
                 if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan launch: %s", hipGetErrorString(r));
                 scanned += upto - pos;
                 scan_len = std::min<uint32_t>(scan_len * 2, 1u << 20);   // still no plain candidates afterwards: the next stretch is twice as long
-                chunk = scan_fast ? 2 : 4;   // (round 6: sixteen rounds of ~40 us between two stretches were a sixth of the dense batch)
+                pace.chunk = scan_fast ? 2 : 4;   // (round 6: sixteen rounds of ~40 us between two stretches were a sixth of the dense batch)
                 after_scan = true;
                 if (node_local && scan_fast && (upto < end || (dbg_bits & 16))) {
                     // Most of the stretch was answered without a look (k_scanb: identical tasks had found no node — a saturated cluster's
@@ -1972,17 +1997,9 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
                 continue;
             }
             after_scan = false;
-            // as many rounds as the rest needs at the pace so far, and a few more: a round past the end costs two empty launches
-            const double pace = std::max(1.0, recent);
-            chunk = (uint32_t)std::min<double>(4096.0, (double)(end - pos) / pace * 1.05 + 4.0);
-            if (scan_ok) chunk = std::min<uint32_t>(chunk, scan_fast ? (recent < 16.0 ? 8u : recent < 64.0 ? 16u : 256u) : (recent < 16.0 ? 16u : recent < 64.0 ? 48u : 256u));   // (look again soon: rounds that hit such a stretch decide one task each)
-            // the block follows the pace: rounds that are cut after a few dozen tasks (re-placements that all aim at the few emptied nodes)
-            // need not propose and stage hundreds of lists each; rounds that fill their block get the next size up
-            if (!env_blk) {
-                if (recent > 0.4 * ra.block) ra.block = std::min<uint32_t>(r6_block, ra.block * 2u);
-                else ra.block = std::min<uint32_t>(r6_block, std::max<uint32_t>(128u, ((uint32_t)(2.0 * recent) + 63u) / 64u * 64u));
-                chunk = std::min<uint32_t>(chunk, ra.block < r6_block ? 64u : 4096u);   // (look again before long while the block is small)
-            }
+            pace.replan(recent);   // the next chunk and the next block (swp_rounds.hpp)
+            ra.block = pace.block;
+            if (scan_ok) pace.chunk = std::min<uint32_t>(pace.chunk, scan_fast ? (recent < 16.0 ? 8u : recent < 64.0 ? 16u : 256u) : (recent < 16.0 ? 16u : recent < 64.0 ? 48u : 256u));   // (look again soon: rounds that hit such a stretch decide one task each)
         }
         if ((dbg_bits & 16) && scanned) fprintf(stderr, "[swp] k_scan decided %u tasks of [%u, %u), %u of them without a look (an identical task had found no node), the others %.2f to a barrier\n", scanned, start, end, hb.scan_skipped, (double)(scanned - hb.scan_skipped) / std::max(1u, hb.scan_batches));
 #ifdef SWP_SCAN_PROF
@@ -2019,34 +2036,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
                 if ((rc = run_blocks(sg.j0, sg.j0 + sg.n))) break;
                 continue;
             }
-            WaterArgs wa{};
-            wa.n_nodes = N;
-            wa.n_words = Wn;
-            wa.xs = Wn;
-            wa.j0 = sg.j0;
-            wa.count = sg.n;
-            wa.rt = b->d_rt.as<RTask>();
-            wa.sc = b->d_sc.as<u64>();
-            wa.cpu = e->d_cpu.as<long long>();
-            wa.mem = e->d_mem.as<long long>();
-            wa.total = e->d_total.as<uint32_t>();
-            wa.X = b->d_X.as<u64>();
-            wa.list_node = b->d_list_node.as<uint32_t>();
-            wa.list_svc = b->d_list_svc.as<uint32_t>();
-            wa.list_fail = b->d_list_fail.as<uint32_t>();
-            wa.list_off = b->d_list_off.as<uint32_t>();
-            wa.out_node = b->d_out.as<int32_t>();
-            wa.log_node = b->d_log_node.as<uint32_t>();
-            wa.log_task = b->d_log_task.as<uint32_t>();
-            wa.log_prev = b->d_log_prev.as<int32_t>();
-            wa.last = b->d_last.as<int32_t>();
-            wa.inf_task = b->d_inf_task.as<uint32_t>();
-            wa.inf_pos = b->d_inf_pos.as<uint32_t>();
-            wa.ctl = b->d_ctl.as<Ctl>();
-            wa.ps = b->d_wf.as<uint32_t>();
-            wa.cap = wa.ps + N;
-            wa.ent = wa.cap + N;
-            hipError_t r = launch_waterfill(wa, st);
+            hipError_t r = launch_waterfill(water_args_for(e, b, sg.j0, sg.n), st);
             if (r != hipSuccess) return e->fail(SWP_EHIP, "k_waterfill launch: %s", hipGetErrorString(r));
             e->stats.waterfill_tasks += sg.n;
         }
@@ -3562,14 +3552,106 @@ int swp_shard_end(swp_engine* e, swp_batch* b, int32_t* out_node_local, uint32_t
     return SWP_OK;
 }
 
-// The block follows the pace (as in the single engine's rounds): rounds that are cut after a few dozen tasks — re-placements that all aim at
-// the few emptied nodes — need not propose and stage hundreds of lists on every shard; rounds that fill their block get the next size up.
-// `recent`: tasks decided per round in the last stretch. The argument records carry the block; the proposals' buffer and the tails stay
-// where the LARGEST block put them. Every rank derives the same size from the same agreed numbers.
-static uint32_t r7_next_block(uint32_t cur, uint32_t largest, double recent) {
-    if (recent > 0.4 * cur) return std::min<uint32_t>(largest, cur * 2u);
-    return std::min<uint32_t>(largest, std::max<uint32_t>(128u, ((uint32_t)(2.0 * recent) + 63u) / 64u * 64u));
+// ---- what swp_shard_run (G engines in one process) and swp_shard_run_rank (one engine per rank) share ---------------------------------
+// The pace — chunk and block from the position and round count read after each chunk — is swp_rounds.hpp's RoundPace, as in the single
+// engine's rounds. The argument records carry the block; the proposals' buffer and the tails stay where the LARGEST block put them.
+namespace {
+// What every shard of a run must agree on before the first launch. It follows from the task list and the node counts of ALL shards, which
+// every rank holds: every rank derives the same plan.
+struct R7Plan {
+    R6Knobs knobs;
+    bool task_rows;      // as soon as one shard's batch wants them
+    bool csi;            // tasks with cluster mounts (the task list is the same on every shard)
+    uint32_t nrr;        // demand-class rows in the commit kernel's LDS
+    uint32_t block;      // the largest block: what the commit kernel's LDS holds next to the TK row of ALL shards' nodes
+    size_t lds_commit;
+};
+void r7_plan(swp_batch* const* batches, uint32_t n_batches, const uint32_t* nodes_per_shard, uint32_t G, R7Plan* p) {
+    p->knobs = r6_knobs(r6_block_max(), R6_BLOCK_DEFAULT_CAP);
+    p->task_rows = false;
+    for (uint32_t g = 0; g < n_batches; ++g) p->task_rows = p->task_rows || r6_task_rows(p->knobs, batches[g]->classes_ok, batches[g]->n_dc + batches[g]->n_dm);
+    p->csi = !batches[0]->csi_set.empty();
+    p->nrr = p->task_rows ? 0u : batches[0]->n_dc + batches[0]->n_dm;
+    uint32_t hw_all = 0;
+    for (uint32_t g = 0; g < G; ++g) hw_all += (nodes_per_shard[g] + 31) / 32;
+    p->block = r6_fit_block(p->knobs.block_cap, [&](uint32_t bl) { return r7_commit_lds_size(hw_all, bl, p->nrr); });
+    p->lds_commit = r7_commit_lds_size(hw_all, p->block, p->nrr);
 }
+
+// The commit kernel's record but for where the proposals and tails lie (the callers' business). `who`: "shards" / "ranks" in the refusals.
+int r7_layout(swp_engine* e, R7Args& ma, const uint32_t* nodes_per_shard, uint32_t G, const R7Plan& plan, const char* who) {
+    ma.n_shards = G;
+    ma.block = plan.block;
+    ma.dbg = plan.knobs.dbg;
+    ma.use_trailers = plan.csi ? 1u : 0u;
+    uint32_t first = 0, hw = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        ma.hw_base[g] = hw;
+        ma.first_node[g] = first;
+        first += nodes_per_shard[g];
+        hw += (nodes_per_shard[g] + 31) / 32;
+    }
+    ma.hw_base[G] = ma.hw_total = hw;
+    if (hw > 0xFFFFu) return e->fail(SWP_ERANGE, "%u nodes over all %s: the commit kernel's half-word indices are 16 bits (2^21 nodes)", first, who);
+    if (plan.lds_commit > R6_LDS_BUDGET) return e->fail(SWP_ERANGE, "%u nodes over all %s with blocks of %u tasks exceed the commit kernel's LDS (SWP_R6_BLOCK)", first, who, plan.block);
+    return SWP_OK;
+}
+
+// One shard, on its engine's stream: state to pristine + class bitmaps (what swp_batch_run does first), the block resolver's argument record
+// and bitmaps, the position at task 0. On return out->prop + plan.block is the shard's tail (the trailer slots: swp_resolve7.hpp), zeroed.
+int r7_shard_setup(swp_engine* e, swp_batch* b, const R7Plan& plan, R6Args* out) {
+    int rc = batch_begin(e, b);
+    if (rc) return rc;
+    if ((rc = r6_args_for(e, b, plan.block, plan.task_rows, plan.knobs.dbg, out))) return rc;
+    out->tmpl = nullptr;   // a range sees only its own part of a level: its lists start at the level's first candidate
+    R7Tail* tail = reinterpret_cast<R7Tail*>(out->prop + plan.block);
+    HIPCHECK(e, hipMemsetAsync(tail, 0, sizeof(R7Tail), e->stream));
+    if (plan.csi) out->trail_out = tail->slot;
+    Blk6 hb{};
+    hb.end = b->T;
+    HIPCHECK(e, hipMemcpyAsync(b->d_blk6.p, &hb, sizeof hb, hipMemcpyHostToDevice, e->stream));
+    const hipError_t r = launch_r6_build(*out, e->stream);
+    if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 build launch: %s", hipGetErrorString(r));
+    return SWP_OK;
+}
+
+// One shard after its last round: explain the unplaceable tasks over its own nodes, results back, every placement checked against the host
+// mirror and (unless SWP_SHARD_NO_FOLD) folded into it, the counters. `hist` may be null; it is written only where done->ninf says so.
+// A placement the mirror does not hold: SWP_EHIP with done->bad_task set and no message (the callers word it).
+struct R7Done { uint32_t ninf = 0, bad_task = 0xFFFFFFFFu; };
+int r7_shard_finish(swp_engine* e, swp_batch* b, uint32_t flags, uint64_t rounds, int32_t* out_local, uint32_t* hist, R7Done* done) {
+    const uint32_t T = b->T;
+    hipStream_t st = e->stream;
+    Ctl ctl{};
+    HIPCHECK(e, hipMemcpyAsync(&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIPCHECK(e, hipStreamSynchronize(st));
+    done->ninf = ctl.ninf;
+    if (ctl.ninf)
+        if (int rc = run_explain(e, b, ctl.ninf)) return rc;
+    HIPCHECK(e, hipMemcpyAsync(out_local, b->d_out.p, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+    if (hist && ctl.ninf) HIPCHECK(e, hipMemcpyAsync(hist, b->d_hist.p, (size_t)T * 8 * 4, hipMemcpyDeviceToHost, st));
+    HIPCHECK(e, hipStreamSynchronize(st));
+    uint64_t placed = 0;
+    for (uint32_t i = 0; i < T; ++i) {
+        const int32_t n = out_local[i];
+        if (n < 0) continue;
+        if ((uint32_t)n >= e->nodes.size() || !e->nodes[n].present) {
+            done->bad_task = i;
+            return SWP_EHIP;
+        }
+        const swp_task_desc& d = b->desc(i);
+        if (!(flags & SWP_SHARD_NO_FOLD)) host_apply_placement(e, (uint32_t)n, d.service, d.cpu, d.mem, d.port_set, !(d.flags & 0x2u), true, d.generic_set);
+        ++placed;
+    }
+    e->stats.batches++;
+    e->stats.tasks += T;
+    e->stats.placed += placed;
+    e->stats.pair_evals += (uint64_t)T * e->n_present;
+    e->stats.last_resolver = 7;   // node-range shards, rounds on the device
+    e->stats.resolve_launches += (uint32_t)rounds;   // (the rounds enqueued)
+    return SWP_OK;
+}
+}  // namespace
 
 int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_t G, uint32_t flags, int32_t* out_shard, int32_t* out_node, uint32_t* out_fail_hist) {
     const auto t_begin = std::chrono::steady_clock::now();
@@ -3589,50 +3671,23 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
     if (out_fail_hist) std::memset(out_fail_hist, 0, (size_t)T * SWP_NFILTERS * 4);
     for (uint32_t i = 0; i < T; ++i) out_shard[i] = out_node[i] = -1;
     if (T == 0) return SWP_OK;
-    const char* env_dbg = getenv("SWP_DBG");
-    const uint32_t dbg_bits = env_dbg ? (uint32_t)atoi(env_dbg) : 0u;
-    const char* env_blk = getenv("SWP_R6_BLOCK");
-    uint32_t block = std::min<uint32_t>(r6_block_max(), std::max<uint32_t>(1u, env_blk ? (uint32_t)atoi(env_blk) : R6_BLOCK_DEFAULT_CAP));   // (as large as the commit kernel's LDS allows: below)
-    const size_t lds_budget = 160 * 1024 - 512;
-    {   // the commit kernel keeps the TK row of ALL shards' nodes next to the block's lists: large node sets get smaller blocks
-        uint32_t hw_all = 0;
-        bool tr = false;
-        for (uint32_t g = 0; g < G; ++g) {
-            hw_all += (engines[g]->n_nodes + 31) / 32;
-            tr = tr || !batches[g]->classes_ok || batches[g]->n_dc + batches[g]->n_dm > 128;
-        }
-        const uint32_t nrr = tr ? 0u : batches[0]->n_dc + batches[0]->n_dm;
-        while (block > 64 && r7_commit_lds_size(hw_all, block, nrr) > lds_budget) block = (block - 1u) / 64u * 64u;
-    }
+    std::vector<uint32_t> shard_nodes(G);
+    for (uint32_t g = 0; g < G; ++g) shard_nodes[g] = engines[g]->n_nodes;
+    R7Plan plan;
+    r7_plan(batches, G, shard_nodes.data(), G, &plan);
+    const uint32_t dbg_bits = plan.knobs.dbg, block = plan.block;
+    const bool csi = plan.csi;
     // one failure anywhere leaves every shard's device rows possibly half-updated: the host mirrors (untouched) are uploaded again
     auto fail_all = [&](int rc) {
         for (uint32_t g = 0; g < G; ++g) engines[g]->dev_dynamic_dirty = true;
         return rc;
     };
-    // per shard: state to pristine + class bitmaps (what swp_batch_run does first), the block resolver's bitmaps, its argument record
+    // per shard: the set-up on its own stream (r7_shard_setup)
     std::vector<R6Args> ra(G);
     R7Args ma{};
-    ma.n_shards = G;
-    ma.block = block;
-    ma.dbg = dbg_bits;
-    uint32_t first = 0, hw = 0;
-    const bool csi = !batches[0]->csi_set.empty();   // (the task list is the same on every shard)
-    ma.use_trailers = csi ? 1u : 0u;
-    const bool task_rows = [&] {
-        const char* env_tr = getenv("SWP_R6_TASKROWS");
-        if (env_tr) return atoi(env_tr) != 0;
-        for (uint32_t g = 0; g < G; ++g)
-            if (!batches[g]->classes_ok || batches[g]->n_dc + batches[g]->n_dm > 128) return true;
-        return false;
-    }();
     for (uint32_t g = 0; g < G; ++g) {
         swp_engine* e = engines[g];
-        swp_batch* b = batches[g];
         (void)hipSetDevice(e->device);
-        ma.hw_base[g] = hw;
-        ma.first_node[g] = first;
-        first += e->n_nodes;
-        hw += (e->n_nodes + 31) / 32;
         for (uint32_t h = 0; h < g; ++h) {   // every shard reads every other shard's proposals: peer memory between their devices
             swp_engine* o = engines[h];
             if (o->device == e->device) continue;
@@ -3650,29 +3705,13 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
         }
         if (e->n_nodes == 0) return e0->fail(SWP_EINVAL, "shard %u owns no node", g);
         const uint32_t Wn = n_words_of(e->n_nodes);
-        if (r6_propose_lds_size(Wn) > lds_budget)
+        if (r6_propose_lds_size(Wn) > R6_LDS_BUDGET)
             return e0->fail(SWP_ERANGE, "shard %u: %u nodes exceed the block resolver's LDS", g, e->n_nodes);
-        int rc = batch_begin(e, b);
-        if (rc) return fail_all(rc);
-        if ((rc = r6_args_for(e, b, block, task_rows, dbg_bits, &ra[g]))) return fail_all(rc);
-        ra[g].tmpl = nullptr;   // a range sees only its own part of a level: its lists start at the level's first candidate
-        R7Tail* tail = reinterpret_cast<R7Tail*>(ra[g].prop + block);   // behind the shard's proposals: the trailer slots
-        ma.tail[g] = tail;
-        HIPCHECK(e, hipMemsetAsync(tail, 0, sizeof(R7Tail), e->stream));
-        if (csi) ra[g].trail_out = tail->slot;
-        Blk6 hb{};
-        hb.pos = 0;
-        hb.end = T;
-        HIPCHECK(e, hipMemcpyAsync(b->d_blk6.p, &hb, sizeof hb, hipMemcpyHostToDevice, e->stream));
-        hipError_t r = launch_r6_build(ra[g], e->stream);
-        if (r != hipSuccess) return fail_all(e0->fail(SWP_EHIP, "k_r6 build launch: %s", hipGetErrorString(r)));
+        if (int rc = r7_shard_setup(e, batches[g], plan, &ra[g])) return fail_all(rc);
         ma.prop[g] = ra[g].prop;
+        ma.tail[g] = reinterpret_cast<R7Tail*>(ra[g].prop + block);
     }
-    ma.hw_base[G] = ma.hw_total = hw;
-    const uint32_t nrr_all = task_rows ? 0u : batches[0]->n_dc + batches[0]->n_dm;
-    const size_t lds_commit = r7_commit_lds_size(hw, block, nrr_all);
-    if (hw > 0xFFFFu) return fail_all(e0->fail(SWP_ERANGE, "%u nodes over all shards: the commit kernel's half-word indices are 16 bits (2^21 nodes)", first));
-    if (lds_commit > lds_budget) return fail_all(e0->fail(SWP_ERANGE, "%u nodes over all shards with blocks of %u tasks exceed the commit kernel's LDS (SWP_R6_BLOCK)", first, block));
+    if (int rc = r7_layout(e0, ma, shard_nodes.data(), G, plan, "shards")) return fail_all(rc);
     // shards that live on one device are served by ONE propose and ONE apply launch per round, on the stream of the first of them
     struct Group { uint32_t g0, count, max_words; int device; hipStream_t stream; DevBuf d_args, d_m; hipEvent_t ev_prop = nullptr, ev_commit = nullptr; };
     std::vector<Group> groups;
@@ -3718,16 +3757,15 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
     }
     const auto t_rounds0 = std::chrono::steady_clock::now();
     // rounds: enqueued blindly, the leader's header read every `chunk` rounds (a round past the end is a handful of empty launches)
-    uint32_t pos = 0, chunk = std::min<uint32_t>(16u, (T + 255u) / 256u + 1u);
+    RoundPace pace(T, block, plan.knobs.block_forced);
     uint64_t rounds = 0;
-    uint32_t cur_block = block, rounds_seen = 0;
     Blk6 hb{};
-    while (pos < T) {
+    while (pace.pos < T) {
         // One round = two launches per device: every shard proposes over its nodes; once the proposals of ALL devices are there (events
         // between the devices' streams; shards of one device share a stream) every shard folds + matches the block itself and applies the
         // picks of its own range. A device's next propose overwrites what the other devices' commit kernels read: it waits for them.
         const bool multi = groups.size() > 1;
-        for (uint32_t r = 0; r < chunk; ++r) {
+        for (uint32_t r = 0; r < pace.chunk; ++r) {
             for (size_t q = 0; q < groups.size(); ++q) {
                 Group& gr = groups[q];
                 (void)hipSetDevice(gr.device);
@@ -3735,7 +3773,7 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
                 if (multi && rounds + r > 0)
                     for (size_t o = 0; o < groups.size() && x == hipSuccess; ++o)
                         if (o != q) x = hipStreamWaitEvent(gr.stream, groups[o].ev_commit, 0);
-                if (x == hipSuccess) x = launch_r7_propose(gr.d_args.as<R6Args>(), gr.count, cur_block, gr.max_words, task_rows, csi, gr.stream, gr.device);
+                if (x == hipSuccess) x = launch_r7_propose(gr.d_args.as<R6Args>(), gr.count, pace.block, gr.max_words, plan.task_rows, csi, gr.stream, gr.device);
                 if (x == hipSuccess && multi) x = hipEventRecord(gr.ev_prop, gr.stream);
                 if (x != hipSuccess) return die(e0->fail(SWP_EHIP, "propose on device %d: %s", gr.device, hipGetErrorString(x)));
             }
@@ -3745,33 +3783,25 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
                 hipError_t x = hipSuccess;
                 for (size_t o = 0; multi && o < groups.size() && x == hipSuccess; ++o)
                     if (o != q) x = hipStreamWaitEvent(gr.stream, groups[o].ev_prop, 0);
-                if (x == hipSuccess) x = launch_r7_commit(gr.d_args.as<R6Args>(), gr.count, gr.d_m.as<R7Args>(), lds_commit, csi, gr.g0, gr.stream, gr.device);
+                if (x == hipSuccess) x = launch_r7_commit(gr.d_args.as<R6Args>(), gr.count, gr.d_m.as<R7Args>(), plan.lds_commit, csi, gr.g0, gr.stream, gr.device);
                 if (x == hipSuccess && multi) x = hipEventRecord(gr.ev_commit, gr.stream);
                 if (x != hipSuccess) return die(e0->fail(SWP_EHIP, "commit on device %d: %s", gr.device, hipGetErrorString(x)));
             }
         }
-        rounds += chunk;
+        rounds += pace.chunk;
         (void)hipSetDevice(e0->device);
         if (hipMemcpyAsync(&hb, batches[0]->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, groups[0].stream) != hipSuccess || hipStreamSynchronize(groups[0].stream) != hipSuccess)
             return die(e0->fail(SWP_EHIP, "reading the leader's control block: %s", hipGetErrorString(hipGetLastError())));
         if (hb.error != ERR_NONE) return die(e0->fail(SWP_ERANGE, "per-node task-count spread exceeds the %d level planes of the block resolver", R6_NP));
-        if (hb.pos <= pos) return die(e0->fail(SWP_EHIP, "sharded rounds made no progress at task %u", pos));
-        const double recent = (double)(hb.pos - pos) / (double)std::max<uint32_t>(hb.rounds - rounds_seen, 1);
-        rounds_seen = hb.rounds;
-        pos = hb.pos;
-        chunk = (uint32_t)std::min<double>(4096.0, (double)(T - pos) / std::max(1.0, recent) * 1.05 + 4.0);
-        if (!env_blk && pos < T) {
-            const uint32_t nb = r7_next_block(cur_block, block, recent);
-            if (nb != cur_block) {
-                cur_block = nb;
-                for (uint32_t g = 0; g < G; ++g) ra[g].block = nb;
-                for (Group& gr : groups) {   // (behind the stretch's kernels on the device's stream)
-                    (void)hipSetDevice(gr.device);
-                    if (hipMemcpyAsync(gr.d_args.p, &ra[gr.g0], (size_t)gr.count * sizeof(R6Args), hipMemcpyHostToDevice, gr.stream) != hipSuccess)
-                        return die(e0->fail(SWP_EHIP, "device %d: %s", gr.device, hipGetErrorString(hipGetLastError())));
-                }
+        if (hb.pos <= pace.pos) return die(e0->fail(SWP_EHIP, "sharded rounds made no progress at task %u", pace.pos));
+        pace.advance(hb.pos, hb.rounds);
+        if (pace.block != ra[0].block) {   // the argument records carry the block
+            for (uint32_t g = 0; g < G; ++g) ra[g].block = pace.block;
+            for (Group& gr : groups) {   // (behind the stretch's kernels on the device's stream)
+                (void)hipSetDevice(gr.device);
+                if (hipMemcpyAsync(gr.d_args.p, &ra[gr.g0], (size_t)gr.count * sizeof(R6Args), hipMemcpyHostToDevice, gr.stream) != hipSuccess)
+                    return die(e0->fail(SWP_EHIP, "device %d: %s", gr.device, hipGetErrorString(hipGetLastError())));
             }
-            if (cur_block < block) chunk = std::min<uint32_t>(chunk, 64u);   // (look again before long while the block is small)
         }
     }
     if (csi) {   // the volumes reserved in the last round: to the shards that did not place that task (every device's rounds are done first)
@@ -3790,7 +3820,7 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
         if (hipStreamSynchronize(gr.stream) != hipSuccess) return die(e0->fail(SWP_EHIP, "device %d: %s", gr.device, hipGetErrorString(hipGetLastError())));
     }
     const auto t_rounds1 = std::chrono::steady_clock::now();
-    // every shard: wait, check, explain the unplaceable tasks over its own nodes, results back, host mirror
+    // every shard: did it see the whole batch? Then its finish (r7_shard_finish); a task belongs to ONE shard, the histograms add up
     std::vector<int32_t> local(T);
     std::vector<uint32_t> hist;
     if (out_fail_hist) hist.resize((size_t)T * SWP_NFILTERS);
@@ -3798,43 +3828,25 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
         swp_engine* e = engines[g];
         swp_batch* b = batches[g];
         (void)hipSetDevice(e->device);
-        Ctl ctl{};
         Blk6 sb{};
-        if (hipMemcpyAsync(&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipMemcpyAsync(&sb, b->d_blk6.p, sizeof sb, hipMemcpyDeviceToHost, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)
+        if (hipMemcpyAsync(&sb, b->d_blk6.p, sizeof sb, hipMemcpyDeviceToHost, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)
             return die(e0->fail(SWP_EHIP, "shard %u: %s", g, hipGetErrorString(hipGetLastError())));
         if (sb.error != ERR_NONE) return die(e0->fail(SWP_ERANGE, "shard %u: per-node task-count spread exceeds the %d level planes", g, R6_NP));
         if (sb.pos != T) return die(e0->fail(SWP_EHIP, "shard %u stopped at task %u of %u", g, sb.pos, T));
-        if (ctl.ninf) {
-            int rc = run_explain(e, b, ctl.ninf);
-            if (rc) return die(rc);
+        R7Done done;
+        if (int rc = r7_shard_finish(e, b, flags, rounds, local.data(), out_fail_hist ? hist.data() : nullptr, &done))
+            return die(done.bad_task != 0xFFFFFFFFu ? e0->fail(SWP_EHIP, "shard %u returned an invalid placement for task %u", g, done.bad_task) : rc);
+        for (uint32_t i = 0; i < T; ++i) {
+            if (local[i] < 0) continue;
+            if (out_shard[i] >= 0) return die(e0->fail(SWP_EHIP, "shard %u returned an invalid placement for task %u", g, i));
+            out_shard[i] = (int32_t)g;
+            out_node[i] = local[i];
         }
-        if (hipMemcpyAsync(local.data(), b->d_out.p, (size_t)T * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return die(e0->fail(SWP_EHIP, "results of shard %u", g));
-        if (out_fail_hist && ctl.ninf && hipMemcpyAsync(hist.data(), b->d_hist.p, (size_t)T * 8 * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
-            return die(e0->fail(SWP_EHIP, "histograms of shard %u", g));
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return die(e0->fail(SWP_EHIP, "shard %u: %s", g, hipGetErrorString(hipGetLastError())));
+        if (out_fail_hist && done.ninf)
+            for (size_t q = 0; q < hist.size(); ++q) out_fail_hist[q] += hist[q];
         if (csi && !(flags & SWP_SHARD_NO_FOLD)) {   // (with SWP_SHARD_NO_FOLD the caller fetches them: the shard set does)
             if (int rcv = download_volumes(e, b, true)) return die(rcv);
         }
-        uint64_t placed = 0;
-        for (uint32_t i = 0; i < T; ++i) {
-            const int32_t nloc = local[i];
-            if (nloc < 0) continue;
-            if ((uint32_t)nloc >= e->nodes.size() || !e->nodes[nloc].present || out_shard[i] >= 0) return die(e0->fail(SWP_EHIP, "shard %u returned an invalid placement for task %u", g, i));
-            out_shard[i] = (int32_t)g;
-            out_node[i] = nloc;
-            const swp_task_desc& d = b->desc(i);
-            if (!(flags & SWP_SHARD_NO_FOLD)) host_apply_placement(e, (uint32_t)nloc, d.service, d.cpu, d.mem, d.port_set, !(d.flags & 0x2u), true, d.generic_set);
-            ++placed;
-        }
-        if (out_fail_hist && ctl.ninf)
-            for (size_t q = 0; q < hist.size(); ++q) out_fail_hist[q] += hist[q];
-        e->stats.batches++;
-        e->stats.tasks += T;
-        e->stats.placed += placed;
-        e->stats.pair_evals += (uint64_t)T * e->n_present;
-        e->stats.last_resolver = 7;   // node-range shards, rounds on the device
-        e->stats.resolve_launches += (uint32_t)rounds;
     }
     if (dbg_bits & 16) {
         Blk6 hh{};
@@ -3843,7 +3855,8 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "[swp] sharded rounds over %u engines: %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, an exception-list task %u, an uncounted task %u | set-up %.2f ms, rounds %.2f ms, explain + results %.2f ms\n", G,
                 hh.rounds, block, (double)T / std::max<uint32_t>(hh.rounds, 1), hh.cut_exhausted, hh.cut_exception, hh.cut_uncounted, ms(t_begin, t_rounds0), ms(t_rounds0, t_rounds1),
-                ms(t_rounds1, std::chrono::steady_clock::now()));        const double rr_ = std::max<uint32_t>(hh.rounds, 1);
+                ms(t_rounds1, std::chrono::steady_clock::now()));
+        const double rr_ = std::max<uint32_t>(hh.rounds, 1);
         fprintf(stderr, "[swp] k_r7_commit (shard 0) shader cycles per round: prologue + fold %.0f, matching (wave 0) %.0f (list loads %.0f, walks %.0f), apply %.0f | %.1f matcher stops at an emptied half-word per round\n",
                 hh.cyc[0] * 64.0 / rr_, hh.cyc[1] * 64.0 / rr_, hh.cyc_load * 64.0 / rr_, hh.cyc_walk * 64.0 / rr_, hh.cyc[3] * 64.0 / rr_, hh.reseats / rr_);
         fprintf(stderr, "[swp] ... of the list loads: waiting for a group's lists %.0f, its head records %.0f, seating %.0f (%.1f steps of the seating loop, stops included) per round\n", hh.cyc_g[0] * 64.0 / rr_,
@@ -3981,19 +3994,11 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
     const uint32_t G = e->rccl_ranks, me = e->rccl_rank, T = b->T;
     (void)hipSetDevice(e->device);
     hipStream_t st = e->stream;
-    const char* env_dbg = getenv("SWP_DBG");
-    const uint32_t dbg_bits = env_dbg ? (uint32_t)atoi(env_dbg) : 0u;
-    const char* env_blk = getenv("SWP_R6_BLOCK");
-    uint32_t block = std::min<uint32_t>(r6_block_max(), std::max<uint32_t>(1u, env_blk ? (uint32_t)atoi(env_blk) : R6_BLOCK_DEFAULT_CAP));   // (as large as the commit kernel's LDS allows: below)
-    const size_t lds_budget = 160 * 1024 - 512;
-    // every rank must choose the same row mode: task rows whenever any rank might (the choice only depends on the task list, which is shared)
-    const char* env_tr = getenv("SWP_R6_TASKROWS");
-    const bool task_rows = env_tr ? atoi(env_tr) != 0 : (!b->classes_ok || b->n_dc + b->n_dm > 128);
-    {   // (and the same block: it follows from shard_nodes and the task list, which every rank holds)
-        uint32_t hw_all = 0;
-        for (uint32_t g = 0; g < G; ++g) hw_all += (shard_nodes[g] + 31) / 32;
-        while (block > 64 && r7_commit_lds_size(hw_all, block, task_rows ? 0u : b->n_dc + b->n_dm) > lds_budget) block = (block - 1u) / 64u * 64u;
-    }
+    // every rank must choose the same row mode and the same block: both follow from shard_nodes and the task list, which every rank holds
+    R7Plan plan;
+    r7_plan(&b, 1, shard_nodes, G, &plan);
+    const uint32_t block = plan.block;
+    const bool csi = plan.csi;
     const uint32_t Wn = n_words_of(e->n_nodes);
     auto bad = [&](int rc) { e->dev_dynamic_dirty = true; (void)hipStreamSynchronize(st); return rc; };
     // ---- everything that can go wrong on THIS rank before the first round is checked here, and the outcome is exchanged: either all
@@ -4001,51 +4006,27 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
     R6Args ra{};
     R7Args ma{};
     DevBuf d_all, d_m, d_args, d_stat;
-    const bool csi = !b->csi_set.empty();
     const size_t send = r7_send_bytes(block);   // what a rank contributes to a round's exchange: its proposals + the tail (swp_resolve7.hpp)
-    size_t lds_commit = 0;
     Blk6 hb{};
     int pre = SWP_OK;
     if (e->n_nodes != b->n_nodes_prepared) pre = e->fail(SWP_EINVAL, "the nodeSet grew since swp_batch_prepare");
     else if (shard_nodes[me] != e->n_nodes) pre = e->fail(SWP_EINVAL, "rank %u holds %u node slots, shard_nodes says %u", me, e->n_nodes, shard_nodes[me]);
     else if (e->n_nodes == 0) pre = e->fail(SWP_EINVAL, "rank %u owns no node", me);
-    else if (r6_propose_lds_size(Wn) > lds_budget) pre = e->fail(SWP_ERANGE, "%u nodes exceed the block resolver's LDS", e->n_nodes);
+    else if (r6_propose_lds_size(Wn) > R6_LDS_BUDGET) pre = e->fail(SWP_ERANGE, "%u nodes exceed the block resolver's LDS", e->n_nodes);
     if (out_fail_hist) std::memset(out_fail_hist, 0, (size_t)T * SWP_NFILTERS * 4);
     for (uint32_t i = 0; i < T; ++i) out_node_local[i] = -1;
     auto setup = [&]() -> int {
-        int rc = batch_begin(e, b);
-        if (rc) return rc;
-        if ((rc = r6_args_for(e, b, block, task_rows, dbg_bits, &ra))) return rc;
-        ra.tmpl = nullptr;   // (as in swp_shard_run)
-        R7Tail* tail = reinterpret_cast<R7Tail*>(ra.prop + block);   // behind this rank's proposals: it travels with them
-        if (csi) ra.trail_out = tail->slot;
-        HIPCHECK(e, hipMemsetAsync(tail, 0, sizeof(R7Tail), st));
-        hb.end = T;
-        HIPCHECK(e, hipMemcpyAsync(b->d_blk6.p, &hb, sizeof hb, hipMemcpyHostToDevice, st));
-        hipError_t x = launch_r6_build(ra, st);
-        if (x != hipSuccess) return e->fail(SWP_EHIP, "k_r6 build launch: %s", hipGetErrorString(x));
+        if (int rc = r7_shard_setup(e, b, plan, &ra)) return rc;   // (the tail behind this rank's proposals travels with them)
         HIPCHECK(e, d_all.reserve((size_t)G * send));
         HIPCHECK(e, d_m.reserve(sizeof(R7Args)));
         HIPCHECK(e, d_args.reserve(sizeof(R6Args)));
         HIPCHECK(e, hipMemcpyAsync(d_args.p, &ra, sizeof ra, hipMemcpyHostToDevice, st));
-        ma.n_shards = G;
-        ma.block = block;
-        ma.dbg = dbg_bits;
-        ma.use_trailers = csi ? 1u : 0u;
         ma.check_dead = 1u;
-        uint32_t first = 0, hw = 0;
         for (uint32_t g = 0; g < G; ++g) {
-            ma.hw_base[g] = hw;
-            ma.first_node[g] = first;
-            first += shard_nodes[g];
-            hw += (shard_nodes[g] + 31) / 32;
             ma.prop[g] = reinterpret_cast<const R6Prop*>(static_cast<const char*>(d_all.p) + (size_t)g * send);   // the layout ncclAllGather leaves
             ma.tail[g] = reinterpret_cast<const R7Tail*>(ma.prop[g] + block);
         }
-        ma.hw_base[G] = ma.hw_total = hw;
-        lds_commit = r7_commit_lds_size(hw, block, task_rows ? 0u : b->n_dc + b->n_dm);
-        if (hw > 0xFFFFu) return e->fail(SWP_ERANGE, "%u nodes over all ranks: the commit kernel's half-word indices are 16 bits (2^21 nodes)", first);
-        if (lds_commit > lds_budget) return e->fail(SWP_ERANGE, "%u nodes over all ranks with blocks of %u tasks exceed the commit kernel's LDS (SWP_R6_BLOCK)", first, block);
+        if (int rc = r7_layout(e, ma, shard_nodes, G, plan, "ranks")) return rc;
         HIPCHECK(e, hipMemcpyAsync(d_m.p, &ma, sizeof ma, hipMemcpyHostToDevice, st));
         // the build kernel's verdict (the level range of THIS rank's nodes) is part of what is exchanged
         HIPCHECK(e, hipMemcpyAsync(&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
@@ -4063,7 +4044,7 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
     default: break;
     }
     if (T == 0) return SWP_OK;
-    uint32_t pos = 0, chunk = std::min<uint32_t>(16u, (T + 255u) / 256u + 1u);
+    RoundPace pace(T, block, plan.knobs.block_forced);
     uint64_t rounds = 0;
     // Inside the rounds NOTHING returns on its own: a rank whose launch / copy failed remembers the first error, marks its tail's dead
     // word, and keeps issuing the chunk's collectives (its peers are enqueued in them) — their commit kernels see the word and stand
@@ -4071,22 +4052,21 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
     int local_rc = SWP_OK;
     auto note = [&](int code) { if (local_rc == SWP_OK) local_rc = code; };
     R7Tail* my_tail = reinterpret_cast<R7Tail*>(ra.prop + block);
-    uint32_t cur_block = block, rounds_seen = 0;
-    while (pos < T) {   // (every rank computes the same positions from the same gathered words, hence the same chunks: the collectives line up)
-        for (uint32_t q = 0; q < chunk; ++q) {
+    while (pace.pos < T) {   // (every rank computes the same positions from the same gathered words, hence the same chunks: the collectives line up)
+        for (uint32_t q = 0; q < pace.chunk; ++q) {
             if (local_rc == SWP_OK) {
-                const hipError_t x = launch_r7_propose(d_args.as<R6Args>(), 1, cur_block, Wn, task_rows, csi, st, e->device);
+                const hipError_t x = launch_r7_propose(d_args.as<R6Args>(), 1, pace.block, Wn, plan.task_rows, csi, st, e->device);
                 if (x != hipSuccess) note(e->fail(SWP_EHIP, "propose: %s", hipGetErrorString(x)));
             }
             if (local_rc != SWP_OK) (void)hipMemsetAsync(&my_tail->dead, 1, sizeof(uint32_t), st);
             const int nr = r->AllGather(ra.prop, d_all.p, send, /* ncclInt8 */ 0, e->rccl_comm, st);
             if (nr != 0) note(e->fail(SWP_EHIP, "ncclAllGather: %s", r->GetErrorString ? r->GetErrorString(nr) : "error"));
             if (local_rc == SWP_OK) {
-                const hipError_t x = launch_r7_commit(d_args.as<R6Args>(), 1, d_m.as<R7Args>(), lds_commit, csi, me, st, e->device);
+                const hipError_t x = launch_r7_commit(d_args.as<R6Args>(), 1, d_m.as<R7Args>(), plan.lds_commit, csi, me, st, e->device);
                 if (x != hipSuccess) note(e->fail(SWP_EHIP, "commit: %s", hipGetErrorString(x)));
             }
         }
-        rounds += chunk;
+        rounds += pace.chunk;
         if (local_rc == SWP_OK && (hipMemcpyAsync(&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
             note(e->fail(SWP_EHIP, "reading the control block: %s", hipGetErrorString(hipGetLastError())));
         if ((rc = rank_agree(e, r, st, d_stat, RankStatus{local_rc, hb.pos, hb.error, hb.rounds}, all))) return bad(rc);   // (the collective itself failed: nothing is left to agree on)
@@ -4096,20 +4076,12 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
         case 3: return bad(e->fail(SWP_EHIP, "the ranks diverged: rank %u stands at task %u, rank 0 at %u", who, all[who].pos, all[0].pos));
         default: break;
         }
-        if (hb.pos <= pos) return bad(e->fail(SWP_EHIP, "sharded rounds made no progress at task %u", pos));   // (the same on every rank: the positions agree)
+        if (hb.pos <= pace.pos) return bad(e->fail(SWP_EHIP, "sharded rounds made no progress at task %u", pace.pos));   // (the same on every rank: the positions agree)
         // (positions and round counts are the agreed ones — rank 0's words, which every rank's equal: the same pace, chunk and block everywhere)
-        const double recent = (double)(all[0].pos - pos) / (double)std::max<uint32_t>(all[0].rounds - rounds_seen, 1);
-        rounds_seen = all[0].rounds;
-        pos = all[0].pos;
-        chunk = (uint32_t)std::min<double>(4096.0, (double)(T - pos) / std::max(1.0, recent) * 1.05 + 4.0);
-        if (!env_blk && pos < T) {
-            const uint32_t nb = r7_next_block(cur_block, block, recent);
-            if (nb != cur_block) {
-                cur_block = nb;
-                ra.block = nb;
-                if (hipMemcpyAsync(d_args.p, &ra, sizeof ra, hipMemcpyHostToDevice, st) != hipSuccess) note(e->fail(SWP_EHIP, "argument record: %s", hipGetErrorString(hipGetLastError())));
-            }
-            if (cur_block < block) chunk = std::min<uint32_t>(chunk, 64u);
+        pace.advance(all[0].pos, all[0].rounds);
+        if (pace.block != ra.block) {
+            ra.block = pace.block;
+            if (hipMemcpyAsync(d_args.p, &ra, sizeof ra, hipMemcpyHostToDevice, st) != hipSuccess) note(e->fail(SWP_EHIP, "argument record: %s", hipGetErrorString(hipGetLastError())));
         }
     }
     if (csi) {   // the volumes reserved in the last round: one more exchange (every rank issues it: the batch ended for all of them together), then every rank takes them
@@ -4118,32 +4090,13 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
         const hipError_t x = launch_r7_settle(d_args.as<R6Args>(), 1, d_m.as<R7Args>(), me, st);
         if (x != hipSuccess) return bad(e->fail(SWP_EHIP, "k_r7_settle: %s", hipGetErrorString(x)));
     }
-    Ctl ctl{};
-    HIPCHECK(e, hipMemcpyAsync(&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIPCHECK(e, hipStreamSynchronize(st));
-    if (ctl.ninf && (rc = run_explain(e, b, ctl.ninf))) return bad(rc);
-    HIPCHECK(e, hipMemcpyAsync(out_node_local, b->d_out.p, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-    if (out_fail_hist && ctl.ninf) HIPCHECK(e, hipMemcpyAsync(out_fail_hist, b->d_hist.p, (size_t)T * 8 * 4, hipMemcpyDeviceToHost, st));
-    HIPCHECK(e, hipStreamSynchronize(st));
+    R7Done done;
+    if ((rc = r7_shard_finish(e, b, flags, rounds, out_node_local, out_fail_hist, &done)))
+        return bad(done.bad_task != 0xFFFFFFFFu ? e->fail(SWP_EHIP, "device returned an invalid node index %d for task %u", out_node_local[done.bad_task], done.bad_task) : rc);
     if (csi) {   // the attachments of this rank's tasks with cluster mounts; the volumes' usage as the batch left it (every rank holds the whole table)
         if (int rcv = download_volumes(e, b, !(flags & SWP_SHARD_NO_FOLD))) return bad(rcv);
         if (flags & SWP_SHARD_NO_FOLD) e->vol_dyn_dirty = true;
     }
-    uint64_t placed = 0;
-    for (uint32_t i = 0; i < T; ++i) {
-        const int32_t n = out_node_local[i];
-        if (n < 0) continue;
-        if ((uint32_t)n >= e->nodes.size() || !e->nodes[n].present) return bad(e->fail(SWP_EHIP, "device returned an invalid node index %d for task %u", n, i));
-        const swp_task_desc& d = b->desc(i);
-        if (!(flags & SWP_SHARD_NO_FOLD)) host_apply_placement(e, (uint32_t)n, d.service, d.cpu, d.mem, d.port_set, !(d.flags & 0x2u), true, d.generic_set);
-        ++placed;
-    }
-    e->stats.batches++;
-    e->stats.tasks += T;
-    e->stats.placed += placed;
-    e->stats.pair_evals += (uint64_t)T * e->n_present;
-    e->stats.last_resolver = 7;
-    e->stats.resolve_launches += (uint32_t)rounds;
     return SWP_OK;
 }
 

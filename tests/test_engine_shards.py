@@ -223,3 +223,105 @@ def test_rank_path_places_task_groups_between_two_sharded_batches():
         got = e.node_get_many(nodes)
         for f in ("cpu", "mem", "total"):
             assert np.array_equal(got[f], want[f]), f
+
+
+# ---- the two device-round drivers share their host rules (csrc/swp_rounds.hpp, the r7_* helpers of csrc/swp_engine.hip) --------------
+# cfg4 with 1500 tasks on 400 nodes: the shape of test_block_size_does_not_matter — over 4 shards ranges of 100 nodes that do not end on
+# a word, and enough tasks for the block to change at least once.
+_CFG4 = {}
+
+
+def _cfg4():
+    """(workload, oracle placements, oracle explanations): computed once, shared, never changed."""
+    if not _CFG4:
+        wl = synth.Workload("cfg4", T=1500, N=400)
+        op, oe, _ = pu.oracle_run(wl)
+        _CFG4["v"] = (wl, op, oe)
+    return _CFG4["v"]
+
+
+def _shard_engines(wl, n_shards):
+    """One engine per node range with the workload loaded and the batch prepared: (schedulers, batches, ranges, task descriptors)."""
+    from swarmkit_amd import host as swhost
+    from swarmkit_amd import shard as swshard
+    ranges = swshard.shard_ranges(wl.N, n_shards)
+    scheds, batches, descs = [], [], None
+    for g, (first, cnt) in enumerate(ranges):
+        s = swhost.HostScheduler(shard_rank=g, shard_count=n_shards)
+        descs = swhost.load_workload(s, wl, first, cnt)
+        scheds.append(s)
+        batches.append(s.e.batch_prepare(descs))
+    return scheds, batches, ranges, descs
+
+
+def _in_oracle_words(wl, sched, out, hist):
+    placed, errs = {}, {}
+    for j in range(wl.T):
+        tid = wl.task_id(j)
+        if out[j] >= 0:
+            placed[tid] = wl.node_id(int(out[j]))
+        else:
+            placed[tid] = None
+            ex = sched.explain(hist[j])
+            errs[tid] = "no suitable node (" + ex + ")" if ex else "no suitable node"
+    return placed, errs
+
+
+def test_one_shard_and_one_rank_are_the_same_driver():
+    """swp_shard_run over ONE shard and swp_shard_run_rank on a job of ONE rank run the same kernels from the same plan at the same pace:
+    equal placements and histograms (both the oracle's), equal counters — resolve_launches counts the rounds ENQUEUED, so equal numbers
+    mean the same chunks, observed on the device — and equal node rows afterwards."""
+    from swarmkit_amd import shard as swshard
+    wl, op, oe = _cfg4()
+    got = []
+    for driver in ("shards", "rank"):
+        (s,), (b,), ranges, _ = _shard_engines(wl, 1)
+        before = s.e.stats()
+        if driver == "shards":
+            out, hist = swshard.DeviceShardGroup([b], [0]).run()
+        else:
+            out, hist = swshard.DeviceRankShard(b, 0, 1, ranges, None, None).run()
+            s.e.rccl_finalize()
+        after = s.e.stats()
+        assert after["last_resolver"] == 7
+        delta = {k: after[k] - before[k] for k in ("batches", "tasks", "placed", "pair_evals", "resolve_launches")}
+        rows = s.e.node_get_many(np.arange(wl.N, dtype=np.uint32))
+        b.free()
+        sp, se = _in_oracle_words(wl, s, out, hist)
+        pu.assert_same(op, oe, sp, se)
+        got.append((np.asarray(out, dtype=np.int64), np.asarray(hist), delta, rows))
+    (out_s, hist_s, delta_s, rows_s), (out_r, hist_r, delta_r, rows_r) = got
+    assert np.array_equal(out_s, out_r) and np.array_equal(hist_s, hist_r)
+    assert delta_s == delta_r and delta_s["batches"] == 1 and delta_s["tasks"] == wl.T and delta_s["resolve_launches"] > 0
+    assert np.array_equal(rows_s, rows_r)
+
+
+@pytest.mark.parametrize("task_rows", ["1", "0"])
+def test_forced_row_mode_over_shards(task_rows, monkeypatch):
+    """SWP_R6_TASKROWS forced either way over 4 shards (cfg3m above reaches task rows only unforced): the block is fitted and the commit
+    kernel's LDS sized with the same row count in both drivers."""
+    monkeypatch.setenv("SWP_R6_TASKROWS", task_rows)
+    wl, op, oe = _cfg4()
+    sp, se, _ = pu.sharded_run(wl, 4, mode="device")
+    pu.assert_same(op, oe, sp, se)
+
+
+def test_refused_calls_leave_the_engines_usable():
+    """Two argument checks of swp_shard_run (they return before anything is launched), then a proper run over the same engines."""
+    from swarmkit_amd import abi
+    from swarmkit_amd import shard as swshard
+    wl, op, oe = _cfg4()
+    scheds, batches, ranges, descs = _shard_engines(wl, 4)
+    with pytest.raises(abi.SwpError) as twice:
+        abi.shard_run([batches[0], batches[0]] + batches[2:])
+    assert twice.value.code == abi.SWP_EINVAL and "shards 0 and 1 name the same engine" in twice.value.msg
+    short = scheds[1].e.batch_prepare(descs[:-1])
+    with pytest.raises(abi.SwpError) as uneven:
+        abi.shard_run([batches[0], short] + batches[2:])
+    assert uneven.value.code == abi.SWP_EINVAL and "shard 1: every shard's batch must hold the same %u tasks" % wl.T in uneven.value.msg
+    short.free()
+    out, hist = swshard.DeviceShardGroup(batches, [r[0] for r in ranges]).run()
+    sp, se = _in_oracle_words(wl, scheds[0], out, hist)
+    for b in batches:
+        b.free()
+    pu.assert_same(op, oe, sp, se)
