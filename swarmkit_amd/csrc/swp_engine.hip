@@ -460,6 +460,7 @@ struct swp_batch {
     // segments of the batch: runs of identical tasks (k_waterfill) and the stretches between them (the resolvers)
     struct Seg { uint32_t j0, n; bool run; };
     std::vector<Seg> segs;
+    bool wide_keys = false;                // an exception entry beyond the 8 + 24 bit keys of k_waterfill and the scan resolver: the block resolver decides alone
     DevBuf d_wf;                           // k_waterfill scratch: [3][n_nodes] u32
     // node-range shard protocol (swp_shard_*): commits / unplaceable tasks of ALL shards so far, this shard's results
     bool shard_open = false, shard_apply_timed = false;
@@ -1267,6 +1268,32 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
         b->max_list = std::max(b->max_list, b->list_off[s + 1] - b->list_off[s]);
     }
     for (uint32_t i = 0; i < T; ++i) b->rt[i].slot = b->list_off[b->rt[i].svc] + init_cnt[b->rt[i].svc] + task_rank[i];
+    // k_waterfill packs (failure class, svcCount) into 8 + 24 bits and gives a node beyond them capacity 0, where nodeLess only ranks
+    // it last: a run of a service with such an entry (259 recorded failures; a count that this batch could carry to 2^24) is decided
+    // by the block resolver
+    b->wide_keys = false;   // (the scan resolver packs the raw failure count into 8 bits: k_scan_lists raises ERR_GROUP_RANGE from 256 on)
+    for (uint32_t s = 0; s < b->n_svc && !b->wide_keys; ++s)
+        for (uint32_t en = b->list_off[s]; en < b->list_off[s] + init_cnt[s]; ++en)
+            if ((uint64_t)b->list_svc0[en] + svc_ntasks[s] >= (1u << 24) || b->list_fail0[en] >= 256u) { b->wide_keys = true; break; }
+    if (b->wide_keys && !b->segs.empty()) {
+        bool changed = false, runs_left = false;
+        for (swp_batch::Seg& sg : b->segs) {
+            if (!sg.run) continue;
+            const uint32_t s = b->rt[sg.j0].svc;
+            for (uint32_t en = b->list_off[s]; en < b->list_off[s] + init_cnt[s] && sg.run; ++en)
+                if ((uint64_t)b->list_svc0[en] + svc_ntasks[s] >= (1u << 24) || b->list_fail0[en] >= 255u + (MAX_FAILURES - 1)) sg.run = false;
+            changed = changed || !sg.run;
+            runs_left = runs_left || sg.run;
+        }
+        if (changed) {
+            std::vector<swp_batch::Seg> merged;
+            for (const swp_batch::Seg& sg : b->segs)
+                if (!merged.empty() && !sg.run && !merged.back().run) merged.back().n += sg.n;
+                else merged.push_back(sg);
+            b->segs = std::move(merged);
+            if (!runs_left) b->segs.clear();
+        }
+    }
 
     mark("exception lists + slots");
     sp.next("build_batch: ports, class tables");
@@ -1913,7 +1940,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
         // measured and lost: device 3.39 -> 3.62 ms a round, same box, three runs each.)
         uint32_t exh_seen = 0, crounds_seen = 0, stops_seen = 0;
         const char* env_scan = getenv("SWP_SCAN");   // 0: never hand a stretch to the scan resolver (tests, A/B runs)
-        const bool scan_ok = N <= scan_max_nodes() && !(env_scan && atoi(env_scan) == 0) && b->csi_set.empty();   // (the scan resolver knows no volumes)
+        const bool scan_ok = N <= scan_max_nodes() && !(env_scan && atoi(env_scan) == 0) && b->csi_set.empty() && !b->wide_keys;   // (the scan resolver knows no volumes, and its keys hold 255 failures and 2^24 - 1 tasks of a service on a node)
         // The batched instance of the scan (k_scanb) decides ~4 tasks a barrier and answers an unplaceable task's twins without a look: where
         // it can run, a stretch goes to it after four poor rounds and two probing rounds follow it; the one-task-a-barrier instance
         // (~1 us a task) has to be worth more: eight poor rounds, four probes

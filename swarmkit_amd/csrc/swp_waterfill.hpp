@@ -119,7 +119,10 @@ __global__ __launch_bounds__(WF_THREADS) void k_waterfill(WaterArgs a) {
             if (cap && r.mem > 0) cap = min(cap, (u64)(m / r.mem));
         }
         if (cap && (r.flags & RT_MAXREP)) cap = r.maxrep > (u64)s ? min(cap, r.maxrep - (u64)s) : 0ull;   // filter.go:373-375
-        if (s >= (1u << 24) || fcl >= 255u) cap = 0;   // beyond the packed key (never in practice): such a node is simply skipped... and flagged
+        // Beyond the packed key (2^24 tasks of the service, 259 recorded failures) the node gets capacity 0 for the whole run: it is
+        // skipped, where nodeLess would only rank it last, and nothing records it. build_batch keeps such runs away from this kernel
+        // (also a count that the batch could carry to 2^24: ps[n] += 1 would run into the class field).
+        if (s >= (1u << 24) || fcl >= 255u) cap = 0;
         a.ps[n] = (fcl << 24) | s;
         a.cap[n] = (u32)min(cap, (u64)0xFFFFFFFFull);
     }

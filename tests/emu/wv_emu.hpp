@@ -1,9 +1,9 @@
 // wv_emu.hpp — CPU implementation of the wave / workgroup primitives of swarmkit_amd/csrc/swp_wave.hpp.
 //
 // TEST INFRASTRUCTURE. One workgroup is run as cooperative fibers (ucontext), one per thread; a collective (ballot,
-// readlane, min, wave_sync, barrier) parks the calling fiber until all 64 lanes of its wave (all threads of the
+// readlane, min, shuffle, wave_sync, barrier) parks the calling fiber until all 64 lanes of its wave (all threads of the
 // workgroup for a barrier) have arrived at the SAME collective, then the last arriver computes the result and releases
-// the others. That is enough to run the kernels' source (swp_resolve6.hpp, swp_resolve7.hpp, swp_scan.hpp, swp_groups.hpp)
+// the others. That is enough to run the kernels' source (swp_resolve6.hpp, swp_resolve7.hpp, swp_scan.hpp, swp_groups.hpp, swp_waterfill.hpp)
 // unchanged and check their control flow, indexing and hand-shakes against a sequential model — not their timing, and not
 // memory-ordering hazards between waves (fibers switch only at collectives). The product never includes this file.
 #pragma once
@@ -41,7 +41,7 @@ namespace emu {
 using swpdev::u32;
 using swpdev::u64;
 
-enum Op { OP_NONE = 0, OP_BALLOT, OP_READLANE, OP_READFIRST, OP_MIN, OP_SYNC, OP_BARRIER, OP_SCAN };
+enum Op { OP_NONE = 0, OP_BALLOT, OP_READLANE, OP_READFIRST, OP_MIN, OP_SYNC, OP_BARRIER, OP_SCAN, OP_SHFL_XOR, OP_SHFL_UP };
 
 // Minimal x86-64 System V context switch (callee-saved registers + stack pointer). glibc's swapcontext makes a
 // sigprocmask system call per switch, and a run makes tens of millions of switches.
@@ -301,6 +301,12 @@ __attribute__((noinline)) inline u64 collective(int op, u64 v, u64 aux) {
         for (u32 l = 0; l < lanes; ++l) { run += ws.vals[l]; ws.result[l] = run; }
         break;
     }
+    case OP_SHFL_XOR:   // __shfl_xor(v, aux, 64): the value of lane ^ aux (a partner beyond a short wave: the lane's own)
+        for (u32 l = 0; l < lanes; ++l) ws.result[l] = ws.vals[((l ^ (u32)aux) & 63u) < lanes ? ((l ^ (u32)aux) & 63u) : l];
+        break;
+    case OP_SHFL_UP:    // __shfl_up(v, aux, 64): the value of lane - aux; lanes below aux keep their own
+        for (u32 l = 0; l < lanes; ++l) ws.result[l] = ws.vals[l >= aux ? l - (u32)aux : l];
+        break;
     default:
         break;
     }
@@ -366,6 +372,10 @@ inline u32 mbcnt(u64 mask) { return (u32)__builtin_popcountll(mask & ((1ull << l
 inline u32 min_u32(u32 v) { return (u32)emu::collective(emu::OP_MIN, v, 0); }
 inline void min4_u32(u32& a, u32& b, u32& c, u32& d) { a = min_u32(a); b = min_u32(b); c = min_u32(c); d = min_u32(d); }
 inline u32 scan_incl_u32(u32 v) { return (u32)emu::collective(emu::OP_SCAN, v, 0); }
+// the raw wave shuffles a kernel written without wv:: primitives uses (swp_waterfill.hpp): the offset rides as `aux`, so a wave whose
+// lanes disagree on it — or on which shuffle they are at — is reported like any other divergence
+inline u64 shfl_xor64(u64 v, u32 off) { return emu::collective(emu::OP_SHFL_XOR, v, off); }
+inline u64 shfl_up64(u64 v, u32 off) { return emu::collective(emu::OP_SHFL_UP, v, off); }
 inline void barrier() { emu::block_barrier(); }
 inline void wave_sync() { (void)emu::collective(emu::OP_SYNC, 0, 0); }
 inline void lockstep() { (void)emu::collective(emu::OP_SYNC, 1, 1); }

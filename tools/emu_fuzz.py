@@ -2,7 +2,7 @@
 fixed case tables of tests/test_emu_*.py name a few dozen shapes each; this draws new ones — seeds, node counts around word and chunk
 borders, block sizes, feature levels, shard counts, option letters — for as long as it is told to and reports every run that does not
 end in "-> OK". No GPU. A failing line is a command to repeat.
-    python tools/emu_fuzz.py [--minutes 30] [--jobs 6] [--seed 1] [--only groups,resolve6,...] [--sched]
+    python tools/emu_fuzz.py [--minutes 30] [--jobs 6] [--seed 1] [--only groups,resolve6,waterfill,...] [--sched]
 --sched: every run also draws a wave SCHEDULE (EMU_SCHED_SEED: which runnable wave goes next, and for how long it keeps going) — the
 hand-shakes between waves that never meet at a barrier under timings the default first-in-first-out order never produces."""
 import argparse
@@ -75,6 +75,9 @@ def draw(rng, which):
         kmax = rng.choice([1, 5, 30, 64, 100, 128, 129, 300, 900])
         trees = rng.choice([1, 1, 2, 3, 4, 6])
         return [seed, n, groups, kmax, trees, rng.randrange(4), rng.choice([128, 256, 512, 1024])] + (["u"] if rng.random() < 0.3 else [])
+    if which == "waterfill":   # emu_waterfill seeded <seed> <N> <len>: node counts around a wave and around 1, 2, 3 nodes a thread of 1024
+        n = rng.choice([1, 2, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049]) if rng.random() < 0.4 else pick_n(rng, 3200)
+        return ["seeded", seed, n, rng.randrange(4)]
     raise ValueError(which)
 
 
@@ -89,7 +92,7 @@ def run(binary, args, sched=0, lvl=None):
         cmd = ["env", "EMU_SCHED_SEED=%d" % sched] + cmd
     t0 = time.time()
     try:
-        r = subprocess.run(cmd + ["v"], capture_output=True, text=True, timeout=1200, env=env)
+        r = subprocess.run(cmd + ([] if args[0] == "seeded" else ["v"]), capture_output=True, text=True, timeout=1200, env=env)
         ok = (r.returncode == 0 and "-> OK" in r.stderr) or "-> SKIP" in r.stderr   # (SKIP: a shape outside the kernel's documented limits)
         tail = r.stderr[-600:]
     except subprocess.TimeoutExpired:
@@ -106,7 +109,8 @@ def main():
     ap.add_argument("--sched", action="store_true", help="every run under its own random wave schedule (EMU_SCHED_SEED)")
     a = ap.parse_args()
     bins = {"resolve6": build("emu_resolve6", "emu_resolve6.cpp"), "resolve7": build("emu_resolve7", "emu_resolve7.cpp"),
-            "scan": build("emu_scan", "emu_scan.cpp"), "groups": build("emu_groups", "emu_groups.cpp"), "groups_small": build("emu_groups_small", "emu_groups.cpp", ["-DG2_ARENA_LDS=3072"])}
+            "scan": build("emu_scan", "emu_scan.cpp"), "groups": build("emu_groups", "emu_groups.cpp"), "groups_small": build("emu_groups_small", "emu_groups.cpp", ["-DG2_ARENA_LDS=3072"]),
+            "waterfill": build("emu_waterfill", "emu_waterfill.cpp")}
     if a.only:
         bins = {k: v for k, v in bins.items() if k in a.only.split(",")}
     rng = random.Random(a.seed)
