@@ -38,7 +38,8 @@ enum {
     SWP_EHIP = -4,         /* HIP runtime error; swp_last_error() has the text */
     SWP_EUNSUPPORTED = -5, /* feature kept on the Go path (CSI volumes, generic reservations of whole task groups, ...) */
     SWP_ERANGE = -6,       /* value outside the engine's documented limits */
-    SWP_ENODEVICE = -7     /* no gfx950 device: the engine has no CPU fallback */
+    SWP_ENODEVICE = -7,    /* no gfx950 device: the engine has no CPU fallback */
+    SWP_ECANCELLED = -8    /* the caller's prefix sink returned non-zero (the streamed entries): the batch was cancelled, nothing was applied */
 };
 
 typedef struct swp_engine swp_engine;
@@ -354,6 +355,36 @@ int swp_batch_results(swp_engine*, swp_batch*, int32_t* out_node, uint32_t* out_
  * whether the choice succeeds or not, volumes.go:104-131,162-178.) After swp_batch_fetch / swp_batch_results. */
 int swp_batch_attachments(swp_engine*, swp_batch*, const uint32_t* tasks, uint32_t n, uint32_t* out);
 void swp_batch_free(swp_engine*, swp_batch*);
+
+/* The streamed run: a batch's placements reach the caller while later rounds still run. The resolvers decide tasks strictly in
+ * order, so a prefix of the batch is final long before its end; the device publishes that prefix to host-visible memory every
+ * SWP_STREAM_EVERY rounds (environment, default 8) and behind every stretch of another resolver, and the call hands each new piece to
+ * `sink` — applySchedulingDecisions (scheduler.go:490-643: one store transaction per 200 decisions) can start on the first piece
+ * instead of waiting for the last round, the copy of all placements and their replay into the node mirror.
+ *   - The sink runs on the calling thread, inside the call.
+ *   - The ranges [first, first + count) are contiguous, ascending and do not overlap; on SWP_OK they cover [0, n_tasks) exactly once.
+ *   - nodes[i] is final: what out_node[first + i] of the plain run holds, -1 ("no suitable node") included. `nodes` points into
+ *     out_node (caller memory); out_node must hold n_tasks entries.
+ *   - Every range but the last holds at least min_tasks tasks. With min_tasks = 0 every publish that moved is one call: the sequence
+ *     of calls is a function of the batch and the knobs, not of host timing.
+ *   - When the sink is called, the node mirror (swp_node_get, swp_node_get_svc_count, swp_node_get_generic) already contains the range.
+ *   - After swp_batch_run_streamed, swp_batch_fetch returns the Explain rows and the attachments and closes the batch; it does not
+ *     fold again (its out_node may be NULL). swp_batch_results is refused.
+ *   - A batch without tasks produces no call. An empty nodeSet: ONE call with every task at -1.
+ *   - A non-zero return from the sink cancels the batch: nothing further is launched and the call returns SWP_ECANCELLED.
+ *   - On ANY return of swp_batch_run_streamed but SWP_OK every range already delivered is void: the engine's mirror and device rows
+ *     are as before the call, out_node is unspecified. (The counters of swp_stats that count launches and resolver work — waterfill_tasks,
+ *     scan_tasks, resolve_launches — keep what the cancelled pass did, as after a failed swp_batch_run.) swp_schedule_batch_streamed is
+ *     prepare + run_streamed + fetch: the same holds for its first two steps; an error of the fetch step alone (a HIP error while the
+ *     Explain rows or the attachments are copied back) is returned with the batch decided, delivered and in the mirror, as it is when
+ *     swp_batch_fetch fails behind swp_batch_run_streamed.
+ *   - A shard set and the shard / rank protocols refuse these entries with SWP_EUNSUPPORTED (nothing is written); task groups
+ *     have no streamed form. */
+typedef int (*swp_prefix_sink)(void* ctx, uint32_t first, uint32_t count, const int32_t* nodes);
+int swp_batch_run_streamed(swp_engine*, swp_batch*, int32_t* out_node, swp_prefix_sink sink, void* ctx, uint32_t min_tasks);
+int swp_schedule_batch_streamed(swp_engine*, const swp_task_desc* tasks, uint32_t n_tasks, int32_t* out_node, uint32_t* out_fail_hist,
+                                swp_prefix_sink sink, void* ctx, uint32_t min_tasks);
+
 /* Device-side snapshot / restore of all mutable node state (cpu, mem, total, per-service counts,
  * host ports) so that a benchmark can replay the same batch from the same state. */
 int swp_state_save(swp_engine*);

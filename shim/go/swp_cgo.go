@@ -31,6 +31,7 @@ import (
 	"context"
 	"fmt"
 	"net"
+	"runtime/cgo"
 	"sort"
 	"strconv"
 	"strings"
@@ -870,6 +871,67 @@ func (sch *Scheduler) scheduleOneOffsSWP(ctx context.Context, tasks []*api.Task,
 		}
 	}
 	return rest
+}
+
+// scheduleOneOffsStreamedSWP: the same batch through swp_schedule_batch_streamed — the placements arrive range by range while later
+// rounds still run, and every range goes straight to the store, applySchedulingDecisions' way (scheduler.go:490-643: one store.Batch
+// transaction per 200 decisions), instead of after the last round, the copy of all placements and their replay into the node mirror.
+// For batches without cluster mounts (their attachments are read after swp_batch_fetch). The C side needs a trampoline, because cgo
+// passes no Go closure as a C function pointer:
+//
+//	//export swpPrefixSink
+//	func swpPrefixSink(ctx unsafe.Pointer, first, count C.uint32_t, nodes *C.int32_t) C.int {
+//		return cgo.Handle(uintptr(ctx)).Value().(func(first int, nodes []C.int32_t) C.int)(int(first), unsafe.Slice(nodes, int(count)))
+//	}
+//
+// and in the preamble: `extern int swpPrefixSink(void*, uint32_t, uint32_t, int32_t*);` (cast to swp_prefix_sink at the call).
+//
+// What is delivered is final (include/swp.h): a task in a range will not move, and the engine's node mirror already holds it. What is NOT
+// known before the call returns is whether the batch as a whole succeeds: on any return but SWP_OK every delivered range is void. So the
+// sink may build and commit store transactions only if the caller can take them back (rollbackSWP's path for a failed transaction), or
+// — as here — it stages the decisions per range (assign() fills `decisions`, which tick() hands to applySchedulingDecisions) and starts
+// the store batch on the ranges it has, committing nothing before the return code is known; a non-zero return from the sink (ctx
+// cancelled) cancels the batch: SWP_ECANCELLED, nothing applied, the Go scan takes the tick.
+func (sch *Scheduler) scheduleOneOffsStreamedSWP(ctx context.Context, kept []*api.Task, descs []C.swp_task_desc, decisions map[string]schedulingDecision) bool {
+	out := make([]C.int32_t, len(descs))
+	hist := make([]C.uint32_t, len(descs)*C.SWP_NFILTERS)
+	staged := 0 // tasks [0, staged) have their decision
+	sink := func(first int, nodes []C.int32_t) C.int {
+		if ctx.Err() != nil {
+			return 1
+		}
+		for i, n := range nodes {
+			if n >= 0 { // (a task without a node needs its Explain row: after the call)
+				sch.assign(ctx, kept[first+i], sch.swp.idxNode[n], nil, decisions)
+			}
+		}
+		staged = first + len(nodes)
+		return 0
+	}
+	h := cgo.NewHandle(sink)
+	defer h.Delete()
+	rc := C.swp_schedule_batch_streamed(sch.swp.e, &descs[0], C.uint32_t(len(descs)), &out[0], &hist[0],
+		C.swp_prefix_sink(C.swpPrefixSink), unsafe.Pointer(uintptr(h)), 200) // min_tasks: a store transaction's worth
+	if rc != C.SWP_OK {
+		// every delivered range is void: the decisions staged for them go, with the NodeInfo.Tasks entries assign() made. NOT through
+		// rollbackSWP: the engine's side is already as before the call, a swp_commit(remove) would take the tasks out twice
+		for _, t := range kept[:staged] {
+			if d, ok := decisions[t.ID]; ok {
+				if ni, err := sch.nodeSet.nodeInfo(d.new.NodeID); err == nil {
+					delete(ni.Tasks, d.new.ID)
+					sch.nodeSet.updateNode(ni)
+				}
+				delete(decisions, t.ID)
+			}
+		}
+		return false
+	}
+	for i, t := range kept {
+		if out[i] < 0 {
+			sch.noSuitableNodeWith(ctx, t, explainFromHist(hist[i*C.SWP_NFILTERS:(i+1)*C.SWP_NFILTERS]), decisions)
+		}
+	}
+	return true
 }
 
 // scheduleGroupsSWP: the grouped branch (scheduler.go:456-461) — every (ServiceID, SpecVersion) group in one call

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "swarmkit_amd", "csrc")
 LIB_PATH = os.environ.get("SWP_LIB_PATH") or os.path.join(ROOT, "swarmkit_amd", "lib", "libswp.so")
 
-SWP_OK, SWP_EINVAL, SWP_ENOTFOUND, SWP_ENOMEM, SWP_EHIP, SWP_EUNSUPPORTED, SWP_ERANGE, SWP_ENODEVICE = 0, -1, -2, -3, -4, -5, -6, -7
+SWP_OK, SWP_EINVAL, SWP_ENOTFOUND, SWP_ENOMEM, SWP_EHIP, SWP_EUNSUPPORTED, SWP_ERANGE, SWP_ENODEVICE, SWP_ECANCELLED = 0, -1, -2, -3, -4, -5, -6, -7, -8
 (SPACE_NODE_ID, SPACE_SERVICE, SPACE_LABEL_KEY, SPACE_FOLDED, SPACE_OS, SPACE_ARCH, SPACE_PLUGIN, SPACE_RAW, SPACE_GENERIC_KIND) = range(9)
 SPACE_VOLUME, SPACE_VOLUME_GROUP, SPACE_CSI = 9, 10, 11
 NODE_READY, NODE_HAS_DESC, NODE_HAS_PLATFORM, NODE_HAS_ENGINE = 0x1, 0x2, 0x4, 0x8
@@ -111,7 +111,7 @@ EXPORTS = [
     "swp_create", "swp_destroy", "swp_reset", "swp_intern", "swp_intern_lookup", "swp_node_upsert", "swp_node_update_dynamic",
     "swp_node_remove", "swp_node_get", "swp_node_set_svc_count", "swp_node_get_svc_count", "swp_node_set_failures", "swp_node_port",
     "swp_constraint_set", "swp_platform_set", "swp_plugin_set", "swp_port_set", "swp_spread_set", "swp_schedule_groups", "swp_schedule_batch", "swp_batch_prepare",
-    "swp_batch_run", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_enforce_generic", "swp_node_matches",
+    "swp_batch_run", "swp_batch_run_streamed", "swp_schedule_batch_streamed", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_enforce_generic", "swp_node_matches",
     "swp_stats", "swp_strerror", "swp_last_error", "swp_abi_check", "swp_node_update_dynamic_many", "swp_node_get_many", "swp_shardset_create",
     "swp_shard_begin", "swp_shard_propose", "swp_shard_merge", "swp_shard_commit", "swp_shard_end", "swp_shard_run", "swp_rccl_available", "swp_rccl_unique_id", "swp_rccl_init", "swp_rccl_finalize", "swp_shard_run_rank", "swp_shard_verdict",
     # include/swp_sched.h — the host layer above the engine
@@ -121,7 +121,9 @@ EXPORTS = [
     "swp_constraint_parse", "swp_key_equal_fold", "swp_explain", "swp_parse_ip",
 ]
 # exports a library built against this header may lack (the host layer's CPU test double): the host layer declares them weak
-OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce_generic"}
+OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce_generic", "swp_batch_run_streamed", "swp_schedule_batch_streamed"}
+# swp_prefix_sink: int (*)(void* ctx, uint32_t first, uint32_t count, const int32_t* nodes) — called on the calling thread, inside the call
+PREFIX_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32))
 MAX_MOUNTS = 8              # SWP_MAX_MOUNTS
 NO_VOLUME = 0xFFFFFFFF      # SWP_NO_VOLUME
 FIT_NO_VOLUME = 8           # SWP_FIT_NO_VOLUME: swp_fit_pairs_volumes' first_fail for a failed chooseTaskVolumes
@@ -197,6 +199,8 @@ def load_library(path=None):
         "swp_batch_prepare": ([vp, vp, u32, P(vp)], C.c_int),
         "swp_batch_prepare_templates": ([vp, vp, u32, vp, u32, P(vp)], C.c_int),
         "swp_batch_run": ([vp, vp], C.c_int),
+        "swp_batch_run_streamed": ([vp, vp, vp, PREFIX_SINK, vp, u32], C.c_int),
+        "swp_schedule_batch_streamed": ([vp, vp, u32, vp, vp, PREFIX_SINK, vp, u32], C.c_int),
         "swp_batch_fetch": ([vp, vp, vp, vp], C.c_int),
         "swp_batch_results": ([vp, vp, vp, vp], C.c_int),
         "swp_batch_free": ([vp, vp], None),
@@ -304,12 +308,38 @@ def shard_merge(proposals, first_nodes, lib_path=None):
     return picks[:acc.value]
 
 
+def _prefix_sink(sink, out):
+    """The CFUNCTYPE object around a Python sink (keep it alive for the call) and the list an exception of the sink lands in: the
+    exception cancels the batch and is raised again once the call has returned."""
+    raised = []
+
+    def cb(_ctx, first, count, _nodes):
+        try:
+            return 1 if sink(int(first), out[first:first + count]) else 0
+        except BaseException as ex:   # noqa: BLE001 — nothing may unwind through the C frames
+            raised.append(ex)
+            return 1
+    return PREFIX_SINK(cb), raised
+
+
 class Batch:
     def __init__(self, eng, handle, n):
         self.eng, self.h, self.n = eng, handle, n
 
     def run(self):
         self.eng._ck(self.eng.L.swp_batch_run(self.eng.h, self.h))
+
+    def run_streamed(self, sink, min_tasks=0):
+        """swp_batch_run_streamed: sink(first, nodes) for every range while later rounds run (nodes: an int32 view into the returned
+        array, valid during the call; a true return value cancels the batch -> SwpError(SWP_ECANCELLED)). Returns out_node int32[T];
+        fetch() afterwards gives the Explain rows and closes the batch."""
+        out = np.empty(self.n, dtype=np.int32)
+        cb, raised = _prefix_sink(sink, out)
+        rc = self.eng.L.swp_batch_run_streamed(self.eng.h, self.h, out.ctypes.data, cb, None, int(min_tasks))
+        if raised:
+            raise raised[0]
+        self.eng._ck(rc)
+        return out
 
     def fetch(self, want_hist=True):
         out = np.empty(self.n, dtype=np.int32)
@@ -597,6 +627,23 @@ class Engine:
         out = np.empty(n, dtype=np.int32)
         hist = np.zeros((n, NFILTERS), dtype=np.uint32) if want_hist else None
         self._ck(self.L.swp_schedule_batch(self.h, tasks.ctypes.data, n, out.ctypes.data, hist.ctypes.data if want_hist else None))
+        return out, hist
+
+    def schedule_batch_streamed(self, tasks, sink, min_tasks=0, want_hist=True):
+        """swp_schedule_batch_streamed: schedule_batch whose placements reach `sink` while later rounds run. sink(first, nodes) is
+        called on this thread for contiguous, ascending ranges that cover the batch exactly once; nodes is an int32 view (valid during
+        the call) of the final placements of tasks first .. first + len(nodes) - 1, and the node mirror already holds them. Every range
+        but the last has at least min_tasks tasks. A true return value (or an exception, raised again here) cancels the batch:
+        SwpError(SWP_ECANCELLED), nothing applied. Returns (out_node int32[T], hist uint32[T,8] or None)."""
+        tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
+        n = len(tasks)
+        out = np.empty(n, dtype=np.int32)
+        hist = np.zeros((n, NFILTERS), dtype=np.uint32) if want_hist else None
+        cb, raised = _prefix_sink(sink, out)
+        rc = self.L.swp_schedule_batch_streamed(self.h, tasks.ctypes.data, n, out.ctypes.data, hist.ctypes.data if want_hist else None, cb, None, int(min_tasks))
+        if raised:
+            raise raised[0]
+        self._ck(rc)
         return out, hist
 
     def batch_prepare(self, tasks):

@@ -29,6 +29,7 @@
 #include "swp_fitpairs.hpp"
 #include "swp_groups.hpp"
 #include "swp_launch.hpp"
+#include "swp_publish.hpp"
 #include "swp_resolve6.hpp"
 #include "swp_resolve7.hpp"
 #include "swp_rounds.hpp"
@@ -462,6 +463,13 @@ struct swp_batch {
     std::vector<Seg> segs;
     bool wide_keys = false;                // an exception entry beyond the 8 + 24 bit keys of k_waterfill and the scan resolver: the block resolver decides alone
     DevBuf d_wf;                           // k_waterfill scratch: [3][n_nodes] u32
+    // the streamed run (swp_batch_run_streamed, swp_publish.hpp): the host-visible block k_publish writes — the mark counter on a line
+    // of its own, the ring of marks, the placements [T] — and the kernel's two device words
+    PinBuf h_pubblk;
+    PinBuf h_words;                        // ... and where the streamed driver reads Blk6 / Ctl back to: pinned, so that the copy never waits on the host
+    DevBuf d_pubstate;
+    bool streamed = false;                 // the last run was a streamed one: its placements are in the node mirror already
+    uint64_t stream_placed = 0;            // ... this many of its tasks found a node
     // node-range shard protocol (swp_shard_*): commits / unplaceable tasks of ALL shards so far, this shard's results
     bool shard_open = false, shard_apply_timed = false;
     uint32_t shard_ncommit = 0, shard_ninf = 0;
@@ -1860,16 +1868,25 @@ WaterArgs water_args_for(swp_engine* e, swp_batch* b, uint32_t j0, uint32_t coun
     return wa;
 }
 
-int batch_run_impl(swp_engine* e, swp_batch* b);
+// the streamed driver's state and its three steps (behind host_apply_bulk, which they fold with)
+struct StreamRun;
+int stream_publish(swp_engine* e, StreamRun* sx, const uint32_t* pos, uint32_t upto);   // enqueue a k_publish (drains first when the ring is nearly full)
+int stream_wait(swp_engine* e, StreamRun* sx, bool drain = false);                       // the stream's work so far, servicing marks meanwhile (drain: and every mark of it)
+uint32_t stream_rounds(const StreamRun* sx);                                             // rounds between two publishes
+int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx = nullptr);
 // Every failure exit of the device pass leaves the device node rows (cpu / mem / total) possibly half-updated — the resolvers commit
 // while they run — so the untouched host mirror is uploaded again before the next device call (as swp_schedule_groups does).
 int batch_run(swp_engine* e, swp_batch* b) {
+    b->streamed = false;
     const int rc = batch_run_impl(e, b);
     if (rc != SWP_OK) e->dev_dynamic_dirty = true;
     return rc;
 }
 
-int batch_run_impl(swp_engine* e, swp_batch* b) {
+// sx != nullptr: the streamed variant — the same launches, the same pace and knobs, with a publish behind every stream_rounds(sx)
+// rounds, every scan stretch and every k_waterfill run; where the plain driver waits for the stream, this one polls an event and hands
+// the marks that arrived to the sink meanwhile (stream_wait). A non-zero code of those steps ends the pass like any other failure.
+int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     if (e->n_nodes != b->n_nodes_prepared)
         return e->fail(SWP_EINVAL, "the nodeSet grew from %u to %u node slots since swp_batch_prepare: prepare the batch again", b->n_nodes_prepared, e->n_nodes);
     const uint32_t N = e->n_nodes, Wn = n_words_of(N), T = b->T;
@@ -1947,10 +1964,26 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
         const bool scan_fast = scan_ok && ra.n_rg == 0 && ra.csi_of == nullptr && scan_batched_fits(N, b->n_svc, b->n_sc);
         while (pos < end) {
             ra.compact = cpt ? (cpt_fused ? 2u : 1u) : 0u;
-            r = launch_r6_rounds(ra, pace.chunk, st, e->device);
+            if (!sx) r = launch_r6_rounds(ra, pace.chunk, st, e->device);
+            else {   // the chunk in pieces, a publish behind each (the chunk's last piece included: a stretch ends published)
+                r = hipSuccess;
+                for (uint32_t done = 0; done < pace.chunk && r == hipSuccess;) {
+                    const uint32_t piece = std::min<uint32_t>(stream_rounds(sx), pace.chunk - done);
+                    r = launch_r6_rounds(ra, piece, st, e->device);
+                    done += piece;
+                    if (r == hipSuccess)
+                        if (int rcp = stream_publish(e, sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rcp;
+                }
+            }
             if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 round launch: %s", hipGetErrorString(r));
-            HIPCHECK(e, hipMemcpyAsync(&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
-            HIPCHECK(e, hipStreamSynchronize(st));
+            // (streamed: into the batch's pinned words — a copy into pageable memory may hold the host until the stream is through, and
+            // the marks are serviced while the host waits, not before)
+            HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : (void*)&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
+            if (sx) {
+                if (int rcw = stream_wait(e, sx)) return rcw;
+                std::memcpy(&hb, b->h_words.p, sizeof hb);
+            } else
+                HIPCHECK(e, hipStreamSynchronize(st));
             if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
             if (hb.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the %d level planes of the block resolver", R6_NP);
             if (hb.pos <= pos) return e->fail(SWP_EHIP, "block resolver made no progress at task %u", pos);   // a round decides its first task at least
@@ -2004,6 +2037,8 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
                 e->scan_stretches_batch += 1;
                 if (r == hipSuccess) r = launch_r6_build(ra, st);   // the rounds go on from the rows as the scan left them
                 if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan launch: %s", hipGetErrorString(r));
+                if (sx)   // (the scan kernels leave Blk6.pos at the end of their stretch)
+                    if (int rcp = stream_publish(e, sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rcp;
                 scanned += upto - pos;
                 scan_len = std::min<uint32_t>(scan_len * 2, 1u << 20);   // still no plain candidates afterwards: the next stretch is twice as long
                 pace.chunk = scan_fast ? 2 : 4;   // (round 6: sixteen rounds of ~40 us between two stretches were a sixth of the dense batch)
@@ -2011,8 +2046,12 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
                 if (node_local && scan_fast && (upto < end || (dbg_bits & 16))) {
                     // Most of the stretch was answered without a look (k_scanb: identical tasks had found no node — a saturated cluster's
                     // backlog): the kernel does that at a hundred tasks a microsecond, a round of the block resolver at ten. On with it.
-                    HIPCHECK(e, hipMemcpyAsync(&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
-                    HIPCHECK(e, hipStreamSynchronize(st));
+                    HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : (void*)&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
+                    if (sx) {
+                        if (int rcw = stream_wait(e, sx)) return rcw;
+                        std::memcpy(&hb, b->h_words.p, sizeof hb);
+                    } else
+                        HIPCHECK(e, hipStreamSynchronize(st));
                     const uint32_t sk = hb.scan_skipped - skipped_seen;
                     skipped_seen = hb.scan_skipped;
                     if (upto < end && 2 * (uint64_t)sk >= upto - pos) {
@@ -2066,14 +2105,20 @@ int batch_run_impl(swp_engine* e, swp_batch* b) {
             hipError_t r = launch_waterfill(water_args_for(e, b, sg.j0, sg.n), st);
             if (r != hipSuccess) return e->fail(SWP_EHIP, "k_waterfill launch: %s", hipGetErrorString(r));
             e->stats.waterfill_tasks += sg.n;
+            if (sx)   // (a run moves no Blk6.pos: its end is the mark)
+                if ((rc = stream_publish(e, sx, nullptr, sg.j0 + sg.n))) break;
         }
     }
     if (rc) return rc;
 
     // explain pass: needs the number of unplaceable tasks (one small D2H, once per batch)
     Ctl ctl{};
-    HIPCHECK(e, hipMemcpyAsync(&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIPCHECK(e, hipStreamSynchronize(st));
+    HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : (void*)&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
+    if (sx) {
+        if ((rc = stream_wait(e, sx, true))) return rc;   // (the resolvers are done: every mark is there, the last range goes out)
+        std::memcpy(&ctl, b->h_words.p, sizeof ctl);
+    } else
+        HIPCHECK(e, hipStreamSynchronize(st));
     if (prof) HIPCHECK(e, hipEventRecord(e->ev[2], st));
     if (ctl.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the resolvers' level planes");
     if (ctl.ninf && (rc = run_explain(e, b, ctl.ninf))) return rc;
@@ -2252,6 +2297,196 @@ void host_apply_bulk(swp_engine* e, const std::vector<BulkItem>& it, bool add, B
     }
 }
 
+// ---- the streamed run (include/swp.h swp_batch_run_streamed) ----
+// What batch_run_impl's streamed variant carries: the marks' arithmetic (swp_rounds.hpp StreamMarks), k_publish's arguments, and the
+// books of what went into the node mirror so far — every failure exit takes exactly that out again.
+struct StreamRun {
+    swp_batch* b;
+    int32_t* out_node;
+    swp_prefix_sink sink;
+    void* ctx;
+    StreamMarks marks;
+    uint32_t every;
+    PubArgs pa{};
+    hipEvent_t ev = nullptr;
+    std::vector<BulkItem> bulk;
+    BulkScratch scr;
+    std::vector<std::pair<uint32_t, uint32_t>> folded;   // (first, count) of the ranges in the mirror, in delivery order
+    std::unordered_map<uint32_t, std::vector<std::pair<uint32_t, int64_t>>> gen_before;   // generic counts of the nodes a fold changed them on, as they were
+    uint64_t placed = 0;
+    StreamRun(swp_batch* b_, int32_t* out, swp_prefix_sink s, void* c, uint32_t min_tasks) : b(b_), out_node(out), sink(s), ctx(c), marks(b_->T, min_tasks), every(stream_every()) {}
+    ~StreamRun() { if (ev) (void)hipEventDestroy(ev); }
+    const uint32_t* h_count() const { return pa.h_count; }
+};
+constexpr size_t PUB_HDR = 64;   // the mark counter's line in front of the ring
+
+uint32_t stream_rounds(const StreamRun* sx) { return sx->every; }
+
+// the pinned block and the device words, as a run starts: no mark, nothing published, every placement the sentinel
+int stream_begin(swp_engine* e, StreamRun* sx) {
+    swp_batch* b = sx->b;
+    const uint32_t T = b->T;
+    // k_publish's stores must reach host DRAM while the kernel runs and be seen by a host that polls: FINE-GRAINED (host-coherent) pinned
+    // memory. The pinned pool allocates with hipHostMallocDefault, i.e. without flags, and that is coherent memory in this runtime
+    // (hipHostMallocNonCoherent, or flags with HIP_HOST_COHERENT=0, would not be); the flags of the block are checked here, so a pool
+    // that one day allocates otherwise is refused instead of streaming stale ranges (the sentinel guard would catch those too).
+    HIPCHECK(e, b->h_pubblk.reserve(PUB_HDR + (size_t)StreamMarks::RING * 4 + (size_t)T * 4));
+    {
+        unsigned int flags = 0;
+        HIPCHECK(e, hipHostGetFlags(&flags, b->h_pubblk.p));
+        if (flags & hipHostMallocNonCoherent) return e->fail(SWP_EHIP, "the pinned block of the streamed run is not host-coherent memory");
+    }
+    HIPCHECK(e, b->h_words.reserve(std::max(sizeof(Blk6), sizeof(Ctl))));
+    HIPCHECK(e, b->d_pubstate.reserve(8));
+    if (!sx->ev) HIPCHECK(e, hipEventCreateWithFlags(&sx->ev, hipEventDisableTiming));
+    char* base = static_cast<char*>(b->h_pubblk.p);
+    PubArgs& pa = sx->pa;
+    pa.n_tasks = T;
+    pa.ring = StreamMarks::RING;
+    pa.out = b->d_out.as<int32_t>();
+    pa.state = b->d_pubstate.as<uint32_t>();
+    pa.h_count = reinterpret_cast<uint32_t*>(base);
+    pa.h_ring = reinterpret_cast<uint32_t*>(base + PUB_HDR);
+    pa.h_pub = reinterpret_cast<int32_t*>(base + PUB_HDR + (size_t)StreamMarks::RING * 4);
+    std::memset(base, 0, PUB_HDR + (size_t)StreamMarks::RING * 4);
+    std::fill(pa.h_pub, pa.h_pub + T, PUB_SENTINEL);
+    HIPCHECK(e, hipMemsetAsync(b->d_pubstate.p, 0, 8, e->stream));
+    return SWP_OK;
+}
+
+// one range: checked, into the mirror, into the caller's array, to the sink
+int stream_deliver(swp_engine* e, StreamRun* sx, uint32_t first, uint32_t count) {
+    swp_batch* b = sx->b;
+    const int32_t* src = sx->pa.h_pub + first;
+    for (uint32_t i = 0; i < count; ++i) {   // nothing of a range is folded before all of it is known to be good
+        const int32_t n = src[i];
+        if (n == PUB_SENTINEL) return e->fail(SWP_EHIP, "published range not visible: task %u of the range [%u, %u) still holds the sentinel", first + i, first, first + count);
+        if (n < -1 || (n >= 0 && ((uint32_t)n >= e->nodes.size() || !e->nodes[n].present))) return e->fail(SWP_EHIP, "device returned an invalid node index %d for task %u", n, first + i);
+    }
+    sx->bulk.clear();
+    for (uint32_t i = 0; i < count; ++i) {
+        const int32_t n = src[i];
+        if (n < 0) continue;
+        const swp_task_desc& d = b->desc(first + i);
+        if (!d.port_set && !d.generic_set && !(d.flags & 0x2u)) sx->bulk.push_back(BulkItem{(uint32_t)n, d.service, d.cpu, d.mem});
+        else {
+            if (d.generic_set && !sx->gen_before.count((uint32_t)n)) sx->gen_before.emplace((uint32_t)n, e->nodes[n].gen);
+            host_apply_placement(e, (uint32_t)n, d.service, d.cpu, d.mem, d.port_set, !(d.flags & 0x2u), true, d.generic_set);
+        }
+        ++sx->placed;
+    }
+    host_apply_bulk(e, sx->bulk, true, sx->scr);
+    sx->folded.emplace_back(first, count);
+    std::memcpy(sx->out_node + first, src, (size_t)count * 4);
+    if (sx->sink && sx->sink(sx->ctx, first, count, sx->out_node + first) != 0) return e->fail(SWP_ECANCELLED, "the sink cancelled the batch at the range [%u, %u)", first, first + count);
+    return SWP_OK;
+}
+
+// the marks that have arrived, in order, until one of them was a delivery or `all` of them are taken (never waits)
+int stream_service(swp_engine* e, StreamRun* sx, bool all) {
+    const uint32_t have = __atomic_load_n(sx->pa.h_count, __ATOMIC_ACQUIRE);
+    if (have - sx->marks.taken > sx->marks.outstanding()) return e->fail(SWP_EHIP, "published range not visible: %u marks on the ring, %u publishes enqueued", have, sx->marks.enqueued);
+    while (sx->marks.taken != have) {
+        const uint32_t mark = __atomic_load_n(&sx->pa.h_ring[sx->marks.taken % StreamMarks::RING], __ATOMIC_RELAXED);
+        uint32_t first = 0, count = 0;
+        const bool due = sx->marks.take(mark, &first, &count);
+        if (sx->marks.bad) return e->fail(SWP_EHIP, "published range not visible: mark %u of %u tasks behind %u", mark, sx->marks.T, sx->marks.top);
+        if (due) {
+            if (int rc = stream_deliver(e, sx, first, count)) return rc;
+            if (!all) break;
+        }
+    }
+    return SWP_OK;
+}
+
+// The host folds and calls the sink only while the device has work queued: one delivery at a time between two looks at the event, and
+// once the event is through the driver goes on enqueuing at once — the marks still on the ring wait for the next call (a fold is
+// 0.1-0.3 ms for a few thousand tasks; done in front of the next chunk's launches it is that much idle device). drain: the caller needs
+// every mark of the work so far (the end of the pass; the ring about to wrap).
+int stream_wait(swp_engine* e, StreamRun* sx, bool drain) {
+    HIPCHECK(e, hipEventRecord(sx->ev, e->stream));
+    for (;;) {
+        const hipError_t q = hipEventQuery(sx->ev);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) return e->fail(SWP_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
+        if (int rc = stream_service(e, sx, false)) return rc;
+    }
+    if (!drain) return SWP_OK;
+    if (int rc = stream_service(e, sx, true)) return rc;
+    if (sx->marks.outstanding()) return e->fail(SWP_EHIP, "published range not visible: %u of %u marks missing behind the stream's work", sx->marks.outstanding(), sx->marks.enqueued);
+    return SWP_OK;
+}
+
+int stream_publish(swp_engine* e, StreamRun* sx, const uint32_t* pos, uint32_t upto) {
+    if (!sx->marks.room())
+        if (int rc = stream_wait(e, sx, true)) return rc;
+    PubArgs pa = sx->pa;
+    pa.pos = pos;
+    pa.upto = upto;
+    const hipError_t r = launch_publish(pa, e->stream);
+    if (r != hipSuccess) return e->fail(SWP_EHIP, "k_publish launch: %s", hipGetErrorString(r));
+    sx->marks.enqueued += 1;
+    return SWP_OK;   // (no look at the ring here: the launches behind this one are what keeps the device busy)
+}
+
+// Every failure exit of the streamed pass — a refusal of the level planes, a HIP error, the sentinel guard, the sink's cancel — is this
+// one path: nothing further is launched (the pass has returned), what is enqueued is waited for, the ranges leave the mirror again in
+// reverse, and the device rows are uploaded again from the mirror before the next device call.
+void stream_rollback(swp_engine* e, StreamRun* sx) {
+    (void)hipStreamSynchronize(e->stream);
+    swp_batch* b = sx->b;
+    for (size_t r = sx->folded.size(); r-- > 0;) {
+        const uint32_t first = sx->folded[r].first, count = sx->folded[r].second;
+        sx->bulk.clear();
+        for (uint32_t i = count; i-- > 0;) {
+            const int32_t n = sx->pa.h_pub[first + i];   // (the engine's own copy: the caller may have written to its array)
+            if (n < 0) continue;
+            const swp_task_desc& d = b->desc(first + i);
+            if (!d.port_set && !d.generic_set && !(d.flags & 0x2u)) sx->bulk.push_back(BulkItem{(uint32_t)n, d.service, d.cpu, d.mem});
+            else host_apply_placement(e, (uint32_t)n, d.service, d.cpu, d.mem, d.port_set, !(d.flags & 0x2u), false);
+        }
+        host_apply_bulk(e, sx->bulk, false, sx->scr);
+    }
+    for (auto& kv : sx->gen_before) e->nodes[kv.first].gen = std::move(kv.second);   // (a removal does not give generic counts back: host_apply_placement)
+    sx->folded.clear();
+    sx->gen_before.clear();
+    e->dev_dynamic_dirty = true;
+    if (!b->csi_set.empty()) e->vol_dyn_dirty = true;   // (the device's usage numbers moved with the rounds, the host's did not)
+    // ... and at once, not at the next swp_batch_prepare: the caller may run this very batch again (a run itself uploads no node rows).
+    // Should the upload fail, the flag stays and the next preparation tries again.
+    (void)flush_nodes(e);
+}
+
+int batch_run_streamed(swp_engine* e, swp_batch* b, int32_t* out_node, swp_prefix_sink sink, void* ctx, uint32_t min_tasks) {
+    b->streamed = false;
+    b->stream_placed = 0;
+    if (e->n_nodes != b->n_nodes_prepared)
+        return e->fail(SWP_EINVAL, "the nodeSet grew from %u to %u node slots since swp_batch_prepare: prepare the batch again", b->n_nodes_prepared, e->n_nodes);
+    const uint32_t T = b->T;
+    if (T == 0) { b->ran = b->streamed = true; return SWP_OK; }
+    if (e->n_nodes == 0) {   // nodeSet is empty: every task is "no suitable node", one range (nothing to fold)
+        std::fill(out_node, out_node + T, -1);
+        if (sink && sink(ctx, 0, T, out_node) != 0) return e->fail(SWP_ECANCELLED, "the sink cancelled the batch at the range [0, %u)", T);
+        b->ran = b->streamed = true;
+        return SWP_OK;
+    }
+    StreamRun sx(b, out_node, sink, ctx, min_tasks);
+    int rc = stream_begin(e, &sx);
+    if (rc == SWP_OK) rc = batch_run_impl(e, b, &sx);
+    if (rc == SWP_OK && !sx.marks.complete())
+        rc = e->fail(SWP_EHIP, "published range not visible: the marks end at task %u of %u", sx.marks.top, T);
+    if (rc != SWP_OK) {
+        const std::string why = e->last_error;   // (the wait below must not replace the reason)
+        stream_rollback(e, &sx);
+        e->last_error = why;
+        b->ran = false;
+        return rc;
+    }
+    b->streamed = true;
+    b->stream_placed = sx.placed;
+    return SWP_OK;
+}
+
 template <class Set, class Index, class Vec>
 int register_set(Index& index, Vec& sets, const std::string& key, Set&& value, uint32_t* id_out) {
     auto it = index.find(key);
@@ -2391,6 +2626,7 @@ const char* swp_strerror(int code) {
     case SWP_EUNSUPPORTED: return "unsupported on the device path";
     case SWP_ERANGE: return "value outside engine limits";
     case SWP_ENODEVICE: return "no gfx950 device (the engine has no CPU fallback)";
+    case SWP_ECANCELLED: return "cancelled by the caller's sink";
     }
     return "unknown error";
 }
@@ -3257,19 +3493,36 @@ int swp_batch_attachments(swp_engine* e, swp_batch* b, const uint32_t* tasks, ui
 
 int swp_batch_fetch(swp_engine* e, swp_batch* b, int32_t* out_node, uint32_t* out_fail_hist) {
     if (e && e->set) return ss::batch_collect(e, b, out_node, out_fail_hist, true);
-    if (!e || !b || (!out_node && b->T)) return SWP_EINVAL;
+    if (!e || !b || (!out_node && b->T && !b->streamed)) return SWP_EINVAL;
     if (!b->ran) return e->fail(SWP_EINVAL, "swp_batch_fetch before swp_batch_run");
     (void)hipSetDevice(e->device);
     const uint32_t T = b->T;
-    if (T == 0) return SWP_OK;
+    if (T == 0) { b->streamed = false; return SWP_OK; }
+    if (b->streamed && e->n_nodes) {
+        // a streamed run: the sink has the placements and the mirror holds them; what is left are the Explain rows, the attachments,
+        // the volumes' usage and the books
+        if (out_node) HIPCHECK(e, hipMemcpyAsync(out_node, b->d_out.p, (size_t)T * 4, hipMemcpyDeviceToHost, e->stream));
+        if (out_fail_hist) {
+            if (int rch = download_hist(e, b, out_fail_hist)) return rch;
+        }
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        if (int rcv = download_volumes(e, b, true)) return rcv;
+        e->stats.batches++;
+        e->stats.tasks += T;
+        e->stats.placed += b->stream_placed;
+        e->stats.infeasible += T - b->stream_placed;
+        e->stats.pair_evals += (uint64_t)T * e->n_present;
+        b->ran = b->streamed = false;
+        return SWP_OK;
+    }
     if (e->n_nodes == 0) {
         // nodeSet is empty: every task is "no suitable node" with an empty explanation
-        for (uint32_t i = 0; i < T; ++i) out_node[i] = -1;
+        for (uint32_t i = 0; i < T && out_node; ++i) out_node[i] = -1;   // (NULL: behind a streamed run, whose sink had the range)
         if (out_fail_hist) std::memset(out_fail_hist, 0, (size_t)T * SWP_NFILTERS * 4);
         e->stats.batches++;
         e->stats.tasks += T;
         e->stats.infeasible += T;
-        b->ran = false;
+        b->ran = b->streamed = false;
         return SWP_OK;
     }
     HostSpan sp("fetch: D2H + wait");
@@ -3309,6 +3562,7 @@ int swp_batch_results(swp_engine* e, swp_batch* b, int32_t* out_node, uint32_t* 
     if (e && e->set) return ss::batch_collect(e, b, out_node, out_fail_hist, false);
     if (!e || !b || (!out_node && b->T)) return SWP_EINVAL;
     if (!b->ran) return e->fail(SWP_EINVAL, "swp_batch_results before swp_batch_run");
+    if (b->streamed) return e->fail(SWP_EINVAL, "swp_batch_results after a streamed run (its placements are in the node mirror): swp_batch_fetch closes it");
     (void)hipSetDevice(e->device);
     if (b->T == 0 || e->n_nodes == 0) return SWP_OK;
     HIPCHECK(e, hipMemcpyAsync(out_node, b->d_out.p, (size_t)b->T * 4, hipMemcpyDeviceToHost, e->stream));
@@ -4125,6 +4379,29 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
         if (flags & SWP_SHARD_NO_FOLD) e->vol_dyn_dirty = true;
     }
     return SWP_OK;
+}
+
+int swp_batch_run_streamed(swp_engine* e, swp_batch* b, int32_t* out_node, swp_prefix_sink sink, void* ctx, uint32_t min_tasks) {
+    if (!e || !b) return SWP_EINVAL;
+    if (e->set || b->is_set) return e->fail(SWP_EUNSUPPORTED, "a shard set has no streamed run");
+    if (b->shard_open) return e->fail(SWP_EUNSUPPORTED, "a batch inside the shard protocol has no streamed run");
+    if (!out_node && b->T) return SWP_EINVAL;
+    (void)hipSetDevice(e->device);
+    return batch_run_streamed(e, b, out_node, sink, ctx, min_tasks);
+}
+
+int swp_schedule_batch_streamed(swp_engine* e, const swp_task_desc* tasks, uint32_t n_tasks, int32_t* out_node, uint32_t* out_fail_hist, swp_prefix_sink sink, void* ctx,
+                                uint32_t min_tasks) {
+    if (!e) return SWP_EINVAL;
+    if (e->set) return e->fail(SWP_EUNSUPPORTED, "a shard set has no streamed run");
+    if (!out_node && n_tasks) return SWP_EINVAL;
+    swp_batch* b = nullptr;
+    int rc = swp_batch_prepare(e, tasks, n_tasks, &b);
+    if (rc) return rc;
+    rc = swp_batch_run_streamed(e, b, out_node, sink, ctx, min_tasks);
+    if (!rc) rc = swp_batch_fetch(e, b, nullptr, out_fail_hist);
+    swp_batch_free(e, b);
+    return rc;
 }
 
 int swp_schedule_batch(swp_engine* e, const swp_task_desc* tasks, uint32_t n_tasks, int32_t* out_node, uint32_t* out_fail_hist) {

@@ -86,4 +86,40 @@ struct RoundPace {
     }
 };
 
+// The streamed driver (swp_batch_run_streamed): behind every `every` rounds, every scan stretch and every k_waterfill run a publish
+// (swp_publish.hpp) copies the decided prefix to host-visible memory and appends its end — a MARK — to a ring. This is what the host
+// makes of the marks: which of them end a delivery to the caller's sink. Marks never go back; a publish that found no progress repeats
+// the last one. A delivery holds at least max(min_tasks, 1) tasks, except the one that ends at T; with min_tasks = 0 every mark that
+// moved is one delivery, so the sequence of calls is a function of the marks alone, never of when the host looked.
+inline uint32_t stream_every() {   // SWP_STREAM_EVERY: rounds between two publishes (default 8)
+    const char* env = getenv("SWP_STREAM_EVERY");
+    const int v = env ? atoi(env) : 8;
+    return (uint32_t)std::min(std::max(v, 1), 4096);
+}
+struct StreamMarks {
+    static constexpr uint32_t RING = 4096;   // marks the ring holds: the driver drains it before that many are outstanding
+    uint32_t T, min_tasks;
+    uint32_t delivered = 0;   // [0, delivered) has gone to the sink
+    uint32_t top = 0;         // the highest mark taken: [0, top) is final and in host memory
+    uint32_t taken = 0;       // marks read off the ring
+    uint32_t enqueued = 0;    // publishes enqueued (each appends exactly one mark)
+    bool bad = false;         // a mark beyond T or behind an earlier one: the ring does not hold what the device wrote
+    StreamMarks(uint32_t n_tasks, uint32_t min_tasks_) : T(n_tasks), min_tasks(min_tasks_) {}
+    // one mark off the ring, in order; true: [*first, *first + *count) is due
+    bool take(uint32_t mark, uint32_t* first, uint32_t* count) {
+        ++taken;
+        if (mark > T || mark < top) { bad = true; return false; }
+        top = mark;
+        const uint32_t pending = top - delivered;
+        if (pending == 0 || (pending < min_tasks && top < T)) return false;
+        *first = delivered;
+        *count = pending;
+        delivered = top;
+        return true;
+    }
+    uint32_t outstanding() const { return enqueued - taken; }
+    bool room() const { return outstanding() + 1u < RING; }        // another publish may be enqueued without a drain first
+    bool complete() const { return !bad && delivered == T; }       // after the last mark: every task went out exactly once
+};
+
 }  // namespace swpdev
