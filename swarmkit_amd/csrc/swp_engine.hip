@@ -432,6 +432,7 @@ struct swp_batch {
     std::vector<uint32_t> rg_kind, rg_k0, rg_k1;   // per row: kind id, first / one-past-last row of the same kind
     std::vector<int32_t> rg_val;
     DevBuf d_tg, d_gs_off, d_gs_row, d_rg_kind, d_rg_k0, d_rg_k1, d_rg_val, d_rg;
+    uint32_t tasks_in_runs = 0;   // of them, in runs of >= 8 consecutive tasks with one descriptor
     std::vector<uint32_t> tmpl;   // [T] the first task with this task's descriptor (identical tasks: swp_resolve6.hpp R6Args.tmpl)
     DevBuf d_tmpl;
     // tasks with cluster mounts (swp_volumes.hpp): csi_of[task] = its index among them (0xFFFFFFFF: none), csi_set[that] = its mount set
@@ -477,6 +478,7 @@ struct swp_batch {
     std::vector<ShardPickDev> shard_mine;  // upload sources of the last commit (alive until the stream has consumed them)
     std::vector<ShardInfDev> shard_infs;
     DevBuf d_prop, d_picks, d_infs;
+    DevBuf d_ext;   // the block resolver's list entries beyond a proposal's (R6PropExt, a single engine's rounds)
     DevBuf d_cmask, d_crank, d_cidx;       // the block resolver's compact index of a round (k_r6_compact)
     // a batch of a shard SET (swp_shardset.hpp): one part per shard, prepared from the same task list; the last run's results
     bool is_set = false;
@@ -1213,6 +1215,14 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
     b->n_plug = (uint32_t)plug_ids.size();
 
     b->tmpl = std::move(tmpl_of);
+    {   // tasks that stand in a run of >= 8 identical tasks: the length from which the commit kernel takes a run's picks by rank (run_blocks)
+        uint32_t in_runs = 0;
+        for (uint32_t i = 0, j; i < T; i = j) {
+            for (j = i + 1; j < T && b->tmpl[j] == b->tmpl[i]; ++j) {}
+            if (j - i >= 8u) in_runs += j - i;
+        }
+        b->tasks_in_runs = in_runs;
+    }
     b->csi_of.clear();
     b->csi_set.clear();
     b->csi_task.clear();
@@ -1908,8 +1918,20 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     const uint32_t dbg_bits = knobs.dbg;
     const bool r6_task_rows = swpdev::r6_task_rows(knobs, b->classes_ok, b->n_dc + b->n_dm);
     const uint32_t r6_nrr = r6_task_rows ? 0u : b->n_dc + b->n_dm;
-    const uint32_t r6_block = r6_fit_block(knobs.block_cap, [&](uint32_t bl) { return r6_commit_lds_size(Wn, bl, r6_nrr); });
-    const bool r6_ok = r6_propose_lds_size(Wn) <= R6_LDS_BUDGET && r6_commit_lds_size(Wn, r6_block, r6_nrr) <= R6_LDS_BUDGET && Wn <= 32768u;   // (half-word indices of 16 bits in the commit kernel's LDS)
+    // (where a compact index may be built, the block leaves the room for its quarter more of TK row)
+    const bool r6_cpt_room = Wn <= R6_COMPACT_MAX_WORDS && b->csi_set.empty();
+    // A batch that is mostly RUNS of identical tasks (service-major order) keeps whole proposals in LDS and the blocks they allow: the
+    // runs-by-rank path (runs of >= 8) takes a run's picks from ONE task's window, and with windows of 16 in blocks of 1 408 service-major
+    // cfg3 — every task in a run of 100 — took 327 rounds and 12.6 ms where the parent took 288 and 10.2 (profiles/late_window.json,
+    // "major_windows_of_16"). Measured at the two ends only — no task in such a run (the headline), every task in one; the line between
+    // them is drawn at half the batch's tasks, counted once when the batch is built. SWP_R6_RUNS=0 / 1 forces either (tests, A/B runs);
+    // SWP_R6_BLOCK still forces the block.
+    const char* env_runs = getenv("SWP_R6_RUNS");
+    const bool r6_runs = env_runs ? atoi(env_runs) != 0 : 2u * (uint64_t)b->tasks_in_runs > T;
+    const uint32_t r6_win = r6_runs ? 32u : 0u;
+    const uint32_t r6_cap = (r6_runs && !knobs.block_forced) ? std::min<uint32_t>(knobs.block_cap, 768u) : knobs.block_cap;
+    const uint32_t r6_block = r6_fit_block(r6_cap, [&](uint32_t bl) { return r6_commit_lds_size(Wn, bl, r6_nrr, r6_cpt_room, r6_win); });
+    const bool r6_ok = r6_propose_lds_size(Wn) <= R6_LDS_BUDGET && r6_commit_lds_size(Wn, r6_block, r6_nrr, false, r6_win) <= R6_LDS_BUDGET && Wn <= 32768u;   // (half-word indices of 16 bits in the commit kernel's LDS)
     if (!r6_ok) return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", N);
     uint32_t wi = 0;   // resolver stretches launched so far (profiling slots)
     uint64_t r6_rounds = 0;
@@ -1924,6 +1946,13 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
             }
         R6Args ra{};
         if (int rc6 = r6_args_for(e, b, r6_block, r6_task_rows, dbg_bits, &ra)) return rc6;
+        HIPCHECK(e, b->d_ext.reserve((size_t)r6_block * sizeof(R6PropExt)));   // lists of R6_LIST half-words: the entries behind a proposal's
+        // (lists beyond a proposal's 32 entries only for full-size blocks of ordinary batches: wave 0 of every propose workgroup pays for
+        // listing them, and neither a batch of runs — its windows hold a whole proposal — nor rounds that are cut after a few dozen
+        // tasks, whose block the pace has shrunk, get anything for it: service-major cfg3 and the churn rounds were slower with them)
+        R6PropExt* const r6_ext = r6_runs ? nullptr : b->d_ext.as<R6PropExt>();
+        ra.ext = r6_ext;
+        ra.win = r6_win;
         if (prof) {
             HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 0], st));
             HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 1], st));
@@ -1946,7 +1975,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
         // one ended if the index was in use then.
         // SWP_R6_COMPACT=0 never, 1 from the first round on (tests, A/B runs).
         const char* env_cpt = getenv("SWP_R6_COMPACT");
-        const bool cpt_ok = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, r6_block, r6_nrr, true) <= R6_LDS_BUDGET && b->csi_set.empty() && !(env_cpt && atoi(env_cpt) == 0);   // (no smaller blocks for it)
+        const bool cpt_ok = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, r6_block, r6_nrr, true, r6_win) <= R6_LDS_BUDGET && b->csi_set.empty() && !(env_cpt && atoi(env_cpt) == 0);   // (no smaller blocks for it)
         bool cpt = cpt_ok && ((env_cpt && atoi(env_cpt) != 0) || e->r6_compact_hint);
         // (the index of the NEXT round built at the end of k_r6_commit_c instead of by a launch of its own: SWP_R6_COMPACT_FUSED=0 for A/B runs)
         const char* env_cf = getenv("SWP_R6_COMPACT_FUSED");
@@ -1994,8 +2023,8 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
             const double recent = pace.observe(hb.pos, hb.rounds);
             if (dbg_bits & 32) fprintf(stderr, "[swp] chunk: %u rounds, %.1f tasks each, at %u of %u | block %u compact %u csize %u clevel %u base %u maxrel %u\n", used, recent, pos, end, ra.block, ra.compact, hb.csize, hb.clevel, hb.base, hb.maxrel);
             {
-                const uint32_t exh = hb.cut_exhausted - exh_seen, cr = hb.crounds - crounds_seen, stops = hb.reseats - stops_seen;
-                exh_seen = hb.cut_exhausted;
+                const uint32_t exh = hb.cut_exhausted + hb.cut_window - exh_seen, cr = hb.crounds - crounds_seen, stops = hb.reseats - stops_seen;
+                exh_seen = hb.cut_exhausted + hb.cut_window;
                 crounds_seen = hb.crounds;
                 stops_seen = hb.reseats;
                 if (cpt && cr) cpt_ever = true;
@@ -2065,6 +2094,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
             after_scan = false;
             pace.replan(recent);   // the next chunk and the next block (swp_rounds.hpp)
             ra.block = pace.block;
+            ra.ext = ra.block < r6_block ? nullptr : r6_ext;
             if (scan_ok) pace.chunk = std::min<uint32_t>(pace.chunk, scan_fast ? (recent < 16.0 ? 8u : recent < 64.0 ? 16u : 256u) : (recent < 16.0 ? 16u : recent < 64.0 ? 48u : 256u));   // (look again soon: rounds that hit such a stretch decide one task each)
         }
         if ((dbg_bits & 16) && scanned) fprintf(stderr, "[swp] k_scan decided %u tasks of [%u, %u), %u of them without a look (an identical task had found no node), the others %.2f to a barrier\n", scanned, start, end, hb.scan_skipped, (double)(scanned - hb.scan_skipped) / std::max(1u, hb.scan_batches));
@@ -2083,8 +2113,8 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
         if (prof) HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 3], st));
         ++wi;
         if (dbg_bits & 16)
-            fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, an exception-list task %u, an uncounted task %u\n", start, end,
-                    hb.rounds, r6_block, (double)(end - start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_exception, hb.cut_uncounted);
+            fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, a window that ran out %u, an exception-list task %u, an uncounted task %u\n", start, end,
+                    hb.rounds, r6_block, (double)(end - start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted);
         if (dbg_bits & 16) {
             const double rr_ = std::max<uint32_t>(hb.rounds, 1);
             fprintf(stderr, "[swp] k_r6_commit shader cycles per round: prologue %.0f, matching (wave 0) %.0f (list loads %.0f, walks %.0f), the others' wait for it %.0f, apply %.0f | %.1f matcher stops at an emptied half-word per round\n",
@@ -3848,7 +3878,7 @@ struct R7Plan {
     size_t lds_commit;
 };
 void r7_plan(swp_batch* const* batches, uint32_t n_batches, const uint32_t* nodes_per_shard, uint32_t G, R7Plan* p) {
-    p->knobs = r6_knobs(r6_block_max(), R6_BLOCK_DEFAULT_CAP);
+    p->knobs = r6_knobs(r7_block_max(), R7_BLOCK_DEFAULT_CAP);
     p->task_rows = false;
     for (uint32_t g = 0; g < n_batches; ++g) p->task_rows = p->task_rows || r6_task_rows(p->knobs, batches[g]->classes_ok, batches[g]->n_dc + batches[g]->n_dm);
     p->csi = !batches[0]->csi_set.empty();

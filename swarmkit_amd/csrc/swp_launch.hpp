@@ -13,9 +13,14 @@ hipError_t ensure_big_lds(const void* fn, int device);
 // k_resolve6, the block resolver (swp_resolve6.hip)
 struct R6Args;
 size_t r6_propose_lds_size(uint32_t n_words);
-size_t r6_commit_lds_size(uint32_t n_words, uint32_t block, uint32_t n_rr, bool compact = false);   // compact: with the room for a compact index (k_r6_compact)
-uint32_t r6_block_max();
-#define R6_BLOCK_DEFAULT_CAP 768u   // tasks per round of the block resolver unless SWP_R6_BLOCK says otherwise (and as the LDS allows)
+size_t r6_commit_lds_size(uint32_t n_words, uint32_t block, uint32_t n_rr, bool compact = false, uint32_t win = 0);   // win: R6Args.win   // compact: with the room for a compact index (k_r6_compact)
+uint32_t r6_block_max();   // the largest block of a single engine ...
+uint32_t r7_block_max();   // ... and of the node-range shards
+// Tasks per round of the block resolver unless SWP_R6_BLOCK says otherwise. A single engine: as many 64-task groups as the commit
+// kernel's LDS holds (windows of R6_WIN list entries a task: 1 408 tasks next to the TK row of 10 000 nodes); the shards, whose commit
+// kernel holds whole folded lists: 768 as far as the LDS allows.
+#define R6_BLOCK_DEFAULT_CAP 2048u
+#define R7_BLOCK_DEFAULT_CAP 768u
 hipError_t launch_r6_build(const R6Args& a, hipStream_t s);
 hipError_t launch_r6_rounds(const R6Args& a, uint32_t rounds, hipStream_t s, int dev);
 

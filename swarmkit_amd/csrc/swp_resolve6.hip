@@ -18,8 +18,9 @@
 namespace swpdev {
 
 size_t r6_propose_lds_size(uint32_t n_words) { return r6_propose_lds(n_words); }
-size_t r6_commit_lds_size(uint32_t n_words, uint32_t block, uint32_t n_rr, bool compact) { return r6_commit_lds(n_words, block, n_rr, compact); }
+size_t r6_commit_lds_size(uint32_t n_words, uint32_t block, uint32_t n_rr, bool compact, uint32_t win) { return r6_commit_lds(n_words, block, n_rr, compact, win); }
 uint32_t r6_block_max() { return R6_BMAX; }
+uint32_t r7_block_max() { return R7_BMAX; }
 
 // base / highest level, then level planes + demand-class rows from the node rows as they are
 hipError_t launch_r6_build(const R6Args& a, hipStream_t s) {
@@ -31,7 +32,7 @@ hipError_t launch_r6_build(const R6Args& a, hipStream_t s) {
 // `rounds` rounds of propose + commit; a round past the end of the stretch is a no-op
 hipError_t launch_r6_rounds(const R6Args& a, uint32_t rounds, hipStream_t s, int dev) {
     const bool cpt = a.compact != 0 && !a.csi_of;   // (a batch with cluster mounts has its own commit instance, without the index)
-    const size_t lp = r6_propose_lds(a.n_words), lc = r6_commit_lds(a.n_words, a.block, a.n_dc + a.n_dm, cpt);
+    const size_t lp = r6_propose_lds(a.n_words), lc = r6_commit_lds(a.n_words, a.block, a.n_dc + a.n_dm, cpt, a.win);
     hipError_t r;
     if (lp > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(cpt ? &k_r6_propose_c : &k_r6_propose), dev)) != hipSuccess) return r;
     if (lc > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(cpt ? &k_r6_commit_c : a.csi_of ? &k_r6_commit_v : &k_r6_commit), dev)) != hipSuccess) return r;
@@ -51,7 +52,9 @@ hipError_t launch_r6_rounds(const R6Args& a, uint32_t rounds, hipStream_t s, int
             hipLaunchKernelGGL(k_r6_commit_c, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, ac);
             continue;
         }
-        if (a.n_words <= R6_SMALL_WORDS) hipLaunchKernelGGL(k_r6_propose_small, dim3(a.block), dim3(64 * R6_PW), lp, s, a);   // (LDS of 8 chunks: never beyond 48 KB)
+        if (a.n_words <= R6_TINY_WORDS && a.block > 1024u) hipLaunchKernelGGL(k_r6_propose_tiny,   // (up to 1 024 workgroups of eight waves are resident together as they are)
+             dim3(a.block), dim3(64 * R6_PW_TINY), lp, s, a);
+        else if (a.n_words <= R6_SMALL_WORDS) hipLaunchKernelGGL(k_r6_propose_small, dim3(a.block), dim3(64 * R6_PW), lp, s, a);   // (LDS of 8 chunks: never beyond 48 KB)
         else hipLaunchKernelGGL(k_r6_propose, dim3(a.block), dim3(64 * R6_PW), lp, s, a);
         if (a.csi_of) hipLaunchKernelGGL(k_r6_commit_v, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, a);
         else hipLaunchKernelGGL(k_r6_commit, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, a);

@@ -16,14 +16,16 @@
 //                  the candidates are narrowed from the top plane down IN REGISTERS (m & ~plane ≠ ∅ ? keep that : the bit is set in
 //                  the word's minimum level); one reduction gives the task's minimum level, the words whose own minimum equals it
 //                  hold exactly its candidates. The first 2 * R6_CAND non-empty half-words go into the task's proposal, with the
-//                  best node of the service's exception list by the full key when there is no plain candidate.
-//   k_r6_commit    one workgroup of 1 024. Every thread stages its task's list into LDS (entry-major). Wave 0 walks the block in
-//                  task order, 64 tasks at a time: a lane seats the first two half-words of its list that still have a candidate
+//                  best node of the service's exception list by the full key when there is no plain candidate; up to R6_LIST in all
+//                  with the side record R6Args.ext.
+//   k_r6_commit    one workgroup of 1 024. LDS holds a window of every task's list (entry-major): its first R6_WIN entries that are live
+//                  when its group is staged — groups 0 and 1 by the prologue, group g by its applying wave two groups ahead of the
+//                  matcher (r6_commit_t). Wave 0 walks the block in task order, 64 tasks at a time: a lane seats the first two half-words of its list that still have a candidate
 //                  (cursor: an entry is looked at once) and wv::match_seq64 gives every task in turn the first listed node nobody
 //                  before it took, struck from every later list. The block is CUT — committed up to there, proposed again from
 //                  there — in front of a task whose listed nodes are all taken, around a task that must use its exception list
 //                  (its order moves with every placement of the service) and behind an uncounted task (its node did NOT move
-//                  up). Waves 1..15 move the cursors of "their" group over dead entries while they wait, then apply the group's
+//                  up). Waves 1..15 (each takes every fifteenth group) move the cursors of "their" group over dead entries while they wait, then apply the group's
 //                  picks: NodeInfo.addTask on the node rows + the bitmaps above + commit log.
 //   k_r6_compact   (only while the host sees the symptom: a matcher stop every few tasks, rounds cut after a fraction of their block)
 //                  one workgroup, in front of the round's propose: numbers the ready nodes on the level the block's first task aims
@@ -48,8 +50,13 @@ namespace swpdev {
 #define R6_CAND 16               // a proposal lists 2 * R6_CAND non-empty 32-node half-words: a block is cut where a task finds all its listed nodes taken
 #endif
 #define R6_SEAT 2                 // list entries a seating step of the matcher looks at (4 measured no better: fewer steps, each longer)
-#define R6_BMAX 1024             // largest block
-#define R6_COMMIT_THREADS 1024      // == R6_BMAX: one accepted pick per thread in the apply phase
+#define R6_BMAX 2048             // largest block of a single engine (waves 1..15 of the commit kernel apply its 64-task groups in turn)
+#define R7_BMAX 1024             // ... of the node-range shards: one group per wave of their commit kernel
+#define R6_COMMIT_THREADS 1024
+#define R6_LIST 64               // half-words the propose kernels list at most: the first 2 * R6_CAND in the proposal, the others in its extension (R6PropExt)
+#ifndef R6_WIN
+#define R6_WIN 16                // list entries of a task the commit kernel keeps in LDS: the first that are live when the task's group is staged
+#endif
 #define R6_NONE 0xFFFFFFFFu
 
 struct Blk6 {   // control block, global memory
@@ -64,8 +71,10 @@ struct Blk6 {   // control block, global memory
     u32 dbg_cut[3];        // dbg: of the cuts at an exhausted list, those whose list was full (more candidates on the level), in compact positions, one entry long
     u32 scan_skipped;      // k_scanb: tasks answered "no node" without a look (an identical task found none earlier in the stretch)
     u32 scan_batches;      // k_scanb: barriers it took for the tasks it did look at
+    u32 cut_window;        // cuts in front of a task whose LDS window ran out while something lay behind it: live entries, entries nobody looked at
+                           // (possibly dead), or more of the level than was listed (bit 31) — an upper bound of the cuts a whole list would have avoided; not in cut_exhausted
 };
-static_assert(sizeof(Blk6) == 112, "Blk6 layout");
+static_assert(sizeof(Blk6) == 116, "Blk6 layout");
 
 struct R6Prop {   // one task's proposal: the shard protocol's record (include/swp.h swp_proposal) with more candidates, as 32-node half-words
     u32 level, n_cand;       // minimum level among the plain candidates (R6_NONE: there is none); half-words listed | bit 31: there are more
@@ -77,6 +86,11 @@ struct R6Prop {   // one task's proposal: the shard protocol's record (include/s
 };
 static_assert(sizeof(R6Prop) == 8 + 12 * R6_CAND + 24, "R6Prop layout");
 static_assert(2 * R6_CAND <= 64, "one lane per list entry");
+struct R6PropExt {   // entries 2 * R6_CAND .. R6_LIST - 1 of a task's list (R6Args.ext): read by k_r6_commit only, never sent between shards
+    unsigned short hw[R6_LIST - 2 * R6_CAND];
+    u32 hb[R6_LIST - 2 * R6_CAND];
+};
+static_assert(R6_WIN >= 1 && R6_WIN <= 2 * R6_CAND && R6_LIST % 16 == 0 && (2 * R6_CAND) % 16 == 0, "the window staging reads 16 entries a batch");
 
 struct R6Args {
     u32 n_nodes, n_words, xs, block;
@@ -149,10 +163,11 @@ struct R6Args {
     // node-range shards (swp_resolve7.hpp): where this shard publishes the volumes of a task with cluster mounts it placed ([2] slots, by
     // round parity, right behind its proposals — they travel with them); nullptr: no volumes in the batch
     struct R7Trail* trail_out;   // = the slots of its R7Tail
+    // [block] the list entries beyond the proposal's; nullptr: lists end with the proposal (the shard drivers: the record they exchange)
+    R6PropExt* ext;
+    u32 win;                 // list entries a task in the commit kernel's LDS (r6_win_of: 0 = R6_WIN); the launch sizes the LDS by it
 };
 struct R7Args;   // swp_resolve7.hpp: what a shard's commit kernel knows of the other shards
-#define R6_STAGES_IN_FLIGHT 2u    // waves that stage their lists at the same time on a single engine (measured, cfg3 / cfg4 1M x 100k: all at once 11.8 / 126.1 ms,
-                                  // 1: 11.6 / 122.7, 2: 11.5 / 122.9, 4: 11.65 / 124.5, 6: 11.7 / 125.6 — the matcher's own group no longer queues behind the others' loads)
 #define R7_FOLDS_IN_FLIGHT 4u   // waves that fold at the same time (the R7 staging below); SWP_DBG bits 8-11 override it for A/B runs (tools/gpu_r5_foldwin.sh)
 #define R7M_EXC 0x100u   // H_meta of a folded record: list length | the task has an exception-list candidate on some shard | it does not count on its node | it has cluster mounts
 #define R7M_UNC 0x200u
@@ -162,18 +177,21 @@ struct R7Args;   // swp_resolve7.hpp: what a shard's commit kernel knows of the 
 #define R6_SMALL_WORDS 512u      // ... on node sets beyond this many words (32 768 nodes); up to there a wave has ONE chunk: a quarter of the registers, so that
                                  // the workgroups of a large block are all resident at once
 #define R6_PW 8                  // waves per task in the propose kernel
+#define R6_PW_TINY 4u            // ... of its instance for node sets of up to R6_TINY_WORDS words (16 384 nodes): a chunk per wave
+#define R6_TINY_WORDS 256u
 inline __host__ __device__ u32 r6_unroll(u32 n_words) { return n_words <= R6_SMALL_WORDS ? 1u : (u32)R6_UNROLL; }
 inline __host__ __device__ u32 r6_chunks(u32 n_words) { const u32 g = r6_unroll(n_words) * R6_PW; return (((n_words + 63u) >> 6) + g - 1u) / g * g; }
 inline __host__ __device__ size_t r6_propose_lds(u32 n_words) { return (size_t)2 * r6_chunks(n_words) * 64 * 8 + 128; }
-// TK row, thresholds, the picks of the block, a few scalars, the block's lists (entry-major)
-// (per task: pick node / index / aux, the cursor, 2 * R6_CAND candidate masks and as many half-word indices of 16 bits: node sets of up to 2^21 nodes)
+// TK row, thresholds, the picks of the block, a few scalars, the block's list windows (entry-major)
+// (per task: pick node / index / aux, the cursor, R6_WIN candidate masks and as many half-word indices of 16 bits: node sets of up to 2^21 nodes)
 // (the TK row: the node words, and in front of them the words of a compact index — at most a quarter of the nodes)
 #define R6_COMPACT_MAX_WORDS 16384u   // node words up to which a compact index may be built (half-word indices are 16 bits in the commit kernel's LDS); the
-                                      // engine builds one only where its quarter more of TK row fits next to the block's lists as they are
+                                      // engine sizes the block of such a node set so that the index's quarter more of TK row fits next to the windows (r6_cpt_room)
 inline __host__ __device__ u32 r6_compact_cap(u32 n_words) { return 16u * n_words; }
 inline __host__ __device__ u32 r6_tk_words(u32 n_words) { return n_words + n_words / 4u + 2u; }   // (with a compact index; n_words otherwise)
-inline __host__ __device__ size_t r6_commit_lds(u32 n_words, u32 block, u32 n_rr, bool compact = false) {
-    return (size_t)((compact ? r6_tk_words(n_words) : n_words) + n_rr) * 8 + (size_t)block * (16 + 2 * R6_CAND * 6) + 128;
+inline __host__ __device__ u32 r6_win_of(u32 win) { return win == 0 ? (u32)R6_WIN : win < 2u * R6_CAND ? win : 2u * R6_CAND; }
+inline __host__ __device__ size_t r6_commit_lds(u32 n_words, u32 block, u32 n_rr, bool compact = false, u32 win = 0) {
+    return (size_t)((compact ? r6_tk_words(n_words) : n_words) + n_rr) * 8 + (size_t)block * (16 + r6_win_of(win) * 6) + 192;
 }
 
 #ifdef SWP_R6_KERNELS   // the kernels: swp_resolve6.hip and the emulation harness only (the engine TU shares the argument records)
@@ -414,7 +432,7 @@ WV_KERNEL(1024) void k_r6_compact(R6Args a) {
 // ---- propose: one workgroup of R6_PW waves per task of the block -----------------------------------------------------------
 // The waves split the task's node words (wave v owns the chunks of 64 words k = v, v + R6_PW, ...): the passes are latency-bound,
 // so more waves per task is what shortens them. A pass ends with one barrier (has any wave a candidate left?).
-template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
+template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(const R6Args& a) {
     const u32 lane = wv::lane(), wave = wv::wave();
     const u32 t = wv::uload(&a.blk->pos) + wv::block();
     if (t >= wv::uload(&a.blk->end) || wv::uload(&a.blk->error) != ERR_NONE) return;   // (an error stops the rounds until the host has seen it)
@@ -422,7 +440,7 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
     const i64 rcpu = wv::uload(&rt->cpu), rmem = wv::uload(&rt->mem);
     const u32 flags = wv::uload(&rt->flags), svc = wv::uload(&rt->svc), scid = wv::uload(&rt->sc), pset = wv::uload(&rt->pset);
     const u64 maxrep = wv::uload(&rt->maxrep);
-    const u32 Wn = a.n_words, KC = r6_chunks(Wn);   // a multiple of UN * R6_PW; the chunks beyond the row hold no candidates
+    const u32 Wn = a.n_words, KC = r6_chunks(Wn);   // a multiple of UN * PW; the chunks beyond the row hold no candidates
     u64* A = wv::lds();
     u64* Bf = A + (size_t)KC * 64;
     u32* flag = reinterpret_cast<u32*>(Bf + (size_t)KC * 64);   // [R6_NP + 2] "some wave still has a candidate", one word per pass
@@ -446,20 +464,20 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
     const u32 ck = a.csi_of ? wv::uload(a.csi_of + t) : R6_NONE;   // a task with cluster mounts: its VolumesFilter row of this round
     const u64* vrow = ck != R6_NONE ? a.vrows + (size_t)ck * a.n_words : nullptr;
     // The task's plain candidates AND the minimum level among them in one pass: lane l of wave v owns words {l + 64 k}, k = v (mod
-    // R6_PW); per word the candidate set is narrowed over the level planes from the top in registers (m & ~plane ≠ ∅ ? keep that : the
+    // PW); per word the candidate set is narrowed over the level planes from the top in registers (m & ~plane ≠ ∅ ? keep that : the
     // bit is set in the word's minimum), the planes of UN words requested together; the minimum over the words is one reduction.
     // How many tasks of the block in front of this one are IDENTICAL to it (same descriptor): each of them takes — strikes — the first
     // candidate nobody took before it, out of the same set in the same order, so when this task's turn comes the first `twins`
     // candidates of the level are gone whatever the other tasks did. Its list starts behind them (below): a block of one service's
     // tasks then walks 32 half-words PER TASK into the level instead of sharing one window of 32. The ids are requested here and
     // counted behind the pass.
-    u32 tw_id[(R6_BMAX + 64 * R6_PW - 1) / (64 * R6_PW)], tw_mine = 0;
+    u32 tw_id[(R6_BMAX + 64 * PW - 1) / (64 * PW)], tw_mine = 0;
     const u32 tw_pos = wv::uload(&a.blk->pos);
     if (a.tmpl) {
         tw_mine = wv::uload(a.tmpl + t);
         WV_UNROLL
-        for (u32 q = 0; q < (R6_BMAX + 64 * R6_PW - 1) / (64 * R6_PW); ++q) {
-            const u32 u = tw_pos + (q * R6_PW + wave) * 64 + lane;
+        for (u32 q = 0; q < (R6_BMAX + 64 * PW - 1) / (64 * PW); ++q) {
+            const u32 u = tw_pos + (q * PW + wave) * 64 + lane;
             tw_id[q] = u < t ? a.tmpl[u] : R6_NONE;
         }
     }
@@ -469,13 +487,13 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
     // the round's compact index (R6Args.compact): VW words of positions, the plain half-words are numbered behind them
     const u32 csize = CPT ? wv::uload(&a.blk->csize) : 0u, VW = (csize + 63u) >> 6;
     u64* V = reinterpret_cast<u64*>(R + (size_t)KC * 64);   // [VW <= KC * 16 + 1] the task's candidates by compact position (the upper half of Bf)
-    for (u32 i = wave * 64 + lane; i < VW; i += 64 * R6_PW) V[i] = 0;
+    for (u32 i = wave * 64 + lane; i < VW; i += 64 * PW) V[i] = 0;
     u32 best = R6_NONE;
-    for (u32 k0 = wave; k0 < KC; k0 += UN * R6_PW) {
+    for (u32 k0 = wave; k0 < KC; k0 += UN * PW) {
         u64 m[UN], f[UN];
         WV_UNROLL
         for (int u = 0; u < UN; ++u) {
-            const u32 w = (k0 + u * R6_PW) * 64 + lane;
+            const u32 w = (k0 + u * PW) * 64 + lane;
             const bool in = w < Wn;
             m[u] = in ? scrow[w] : 0ull;
             f[u] = in ? xrow[w] : 0ull;
@@ -487,7 +505,7 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
         u32 rel[UN];
         WV_UNROLL
         for (int u = 0; u < UN; ++u) {
-            const u32 w = (k0 + u * R6_PW) * 64 + lane;
+            const u32 w = (k0 + u * PW) * 64 + lane;
             m[u] &= ~f[u];
             for (u32 p = p0; p < p1; ++p)
                 if (m[u]) m[u] &= ~a.portmap[(size_t)wv::uload(a.pset_ids + p) * Wn + w];
@@ -498,7 +516,7 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
             u64 q[UN][8];
             WV_UNROLL
             for (int u = 0; u < UN; ++u) {
-                const u32 w = (k0 + u * R6_PW) * 64 + lane;
+                const u32 w = (k0 + u * PW) * 64 + lane;
                 // (a word without candidates needs no planes — but on a small node set waiting for m costs more than the loads: there the top
                 // batch is requested together with the rows)
                 const bool want = (hi == nb && Wn <= 512u) ? w < Wn : m[u] != 0;   // m != 0 only inside the row
@@ -518,7 +536,7 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
         }
         WV_UNROLL
         for (int u = 0; u < UN; ++u) {
-            const u32 idx = (k0 + u * R6_PW) * 64 + lane;
+            const u32 idx = (k0 + u * PW) * 64 + lane;
             A[idx] = m[u];
             const u32 r = m[u] ? rel[u] : R6_NONE;
             R[idx] = r;
@@ -529,17 +547,17 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
     u32 tw_cnt = 0;
     if (a.tmpl) {
         WV_UNROLL
-        for (u32 q = 0; q < (R6_BMAX + 64 * R6_PW - 1) / (64 * R6_PW); ++q) tw_cnt += (u32)wv::popc64(wv::ballot(tw_id[q] == tw_mine && tw_pos + (q * R6_PW + wave) * 64 + lane < t));
+        for (u32 q = 0; q < (R6_BMAX + 64 * PW - 1) / (64 * PW); ++q) tw_cnt += (u32)wv::popc64(wv::ballot(tw_id[q] == tw_mine && tw_pos + (q * PW + wave) * 64 + lane < t));
     }
     if (lane == 0) {
         flag[wave] = best;
-        flag[R6_PW + wave] = tw_cnt;
+        flag[PW + wave] = tw_cnt;
     }
     wv::barrier();
     u32 gmin = R6_NONE, twins = 0;
-    for (u32 v = 0; v < R6_PW; ++v) {
+    for (u32 v = 0; v < PW; ++v) {
         gmin = min(gmin, flag[v]);
-        twins += flag[R6_PW + v];
+        twins += flag[PW + v];
     }
     const u32 level = gmin == R6_NONE ? R6_NONE : wv::uload(&a.blk->base) + gmin;
     // the task's minimum level is the compact index's: its candidates are among the index's nodes; every wave moves those of its share of
@@ -547,7 +565,7 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
     const bool cmode = CPT && csize != 0 && gmin == wv::uload(&a.blk->clevel);
     if (CPT && cmode) {
         u32* V32 = reinterpret_cast<u32*>(V);
-        for (u32 idx = wave * 64 + lane; idx < Wn; idx += 64 * R6_PW) {
+        for (u32 idx = wave * 64 + lane; idx < Wn; idx += 64 * PW) {
             u64 m = R[idx] == gmin ? A[idx] : 0ull;
             if (!m) continue;
             const u64 cm = a.cmask[idx];
@@ -566,6 +584,8 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
     R6Prop* out = a.prop + wv::block();
     // its first non-empty half-words, in node order (what the matcher walks: a word that is half empty does not cost a list entry):
     // 64 words a step, a lane's place in the list = the non-empty half-words in front of it (two ballots)
+    R6PropExt* ext = a.ext ? a.ext + wv::block() : nullptr;
+    const u32 lmax = ext ? (u32)R6_LIST : 2u * R6_CAND;
     u32 cnt = 0, more = 0;
     u32 skip = twins, last_hw = 0, last_hb = 0;   // candidates still to pass over; the last non-empty half-word passed over
     if (level != R6_NONE)
@@ -611,14 +631,20 @@ template <int UN, bool CPT = false> WV_DEV void r6_propose_t(const R6Args& a) {
             if (lo && at_lo < 2 * R6_CAND) {
                 out->hw[at_lo] = (unsigned short)(hw_off + 2 * (k * 64 + lane));
                 out->hb[at_lo] = lo;
+            } else if (lo && at_lo < lmax) {
+                ext->hw[at_lo - 2 * R6_CAND] = (unsigned short)(hw_off + 2 * (k * 64 + lane));
+                ext->hb[at_lo - 2 * R6_CAND] = lo;
             }
             if (hi && at_hi < 2 * R6_CAND) {
                 out->hw[at_hi] = (unsigned short)(hw_off + 2 * (k * 64 + lane) + 1);
                 out->hb[at_hi] = hi;
+            } else if (hi && at_hi < lmax) {
+                ext->hw[at_hi - 2 * R6_CAND] = (unsigned short)(hw_off + 2 * (k * 64 + lane) + 1);
+                ext->hb[at_hi - 2 * R6_CAND] = hi;
             }
             const u32 total = cnt + (u32)wv::popc64(b_lo) + (u32)wv::popc64(b_hi);
-            if (total > 2 * R6_CAND) more = 1;
-            cnt = min(total, (u32)(2 * R6_CAND));
+            if (total > lmax) more = 1;
+            cnt = min(total, lmax);
         }
     // no plain candidate: the service's exception list by the full key (scheduler.go:708-735), lanes stride over the entries
     u64 bhi = KEY_NONE, blo = KEY_NONE;
@@ -684,6 +710,9 @@ WV_DEV void r6_propose(const R6Args& a) {
 }
 WV_KERNEL(64 * R6_PW) void k_r6_propose(R6Args a) { r6_propose(a); }
 WV_KERNEL(64 * R6_PW) void k_r6_propose_small(R6Args a) { r6_propose_t<1>(a); }   // n_words <= R6_SMALL_WORDS only: the registers of ONE chunk
+// n_words <= R6_TINY_WORDS only: four waves a task, each with one chunk — half the threads, so that the workgroups of a block of 1 408
+// are all resident at once (8 to a CU); at 157 node words three of eight waves had a word at all
+WV_KERNEL(64 * R6_PW_TINY) void k_r6_propose_tiny(R6Args a) { r6_propose_t<1, false, R6_PW_TINY>(a); }
 // ... the instances that honour a round's compact index (launched behind k_r6_compact only)
 WV_KERNEL(64 * R6_PW) void k_r6_propose_c(R6Args a) {
     if (a.n_words <= R6_SMALL_WORDS) r6_propose_t<1, true>(a);
@@ -728,23 +757,35 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     u32* pk_idx = pk_node + a.block;                             // [block] commit index / index among the unplaceable tasks
     u32* pk_aux = pk_idx + a.block;                              // [block] exception-list entry (LIST_EMPTY: plain node) / commits before an unplaceable task
     u32* sh = pk_aux + a.block;                                  // [0] accepted, [1] ncommit, [2] ninf, [3] tasks decided so far, [4] the matching is over
-    u32* staged = sh + 16;                                       // [16] group g's lists are in LDS
-    u32* L_hb = sh + 32;                                         // [2 * R6_CAND][block] the block's lists, entry-major: lane i of the matcher reads
-    u32* L_cur = L_hb + (size_t)2 * R6_CAND * a.block;           // ... entry k of task i at [k * block + i] (no bank conflicts); [block] a lower bound of every task's cursor: the entries in front of it are dead
-    unsigned short* L_hw = reinterpret_cast<unsigned short*>(L_cur + a.block);   // [2 * R6_CAND][block] the half-word indices, 16 bits each (the engine refuses node sets beyond 2^21 nodes)
-    u32* H_level = reinterpret_cast<u32*>(L_hw + (size_t)2 * R6_CAND * a.block);   // R7 only: [block] the folded record's level ...
-    u32* H_meta = H_level + a.block;                                                // ... and its list length | R7M_* flags
+    u32* staged = sh + 16;                                       // [R6_BMAX / 64] group g's lists are in LDS
+    // The lists in LDS, LW entries a task. R7: the whole folded list, staged by the prologue. Otherwise a WINDOW: the first `win` entries
+    // that are live when the task's group is staged — groups 0 and 1 by the prologue (nothing is taken yet: the list's first entries),
+    // group g >= 2 by the wave that will apply it, against the TK row once the matcher has published the picks of group g - 2. Taken
+    // nodes stay taken, so what is dead then is dead; what dies later meets the seating step's own TK test. A task whose window runs
+    // out while entries were left out of it is treated as one whose list is exhausted: the block is cut in front of it (a cut is
+    // always allowed) and counted in Blk6.cut_window.
+    // (R6Args.win: the engine gives batches of long runs of identical tasks windows of 2 * R6_CAND in blocks of 768 — the runs-by-rank path
+    // takes a whole run from ONE task's window, and service-major cfg3 lost a fifth with windows of 16)
+    constexpr u32 LMAX = 2u * R6_CAND;
+    const u32 LW = R7 ? LMAX : r6_win_of(a.win);   // rows of the two arrays
+    const u32 win = (R7 || !((a.dbg >> 12) & 31u)) ? LW : min((a.dbg >> 12) & 31u, LW);   // (dbg bits 12-16: a shorter window, tests)
+    u32* L_hb = sh + 48;                                         // [LW][block] entry-major: lane i of the matcher reads
+    u32* L_cur = L_hb + (size_t)LW * a.block;                    // ... entry k of task i at [k * block + i] (no bank conflicts); [block] a lower bound of every task's cursor: the entries in front of it are dead
+                                                                 // (not R7: | entries in the window << 8 | something was left out of it << 16)
+    unsigned short* L_hw = reinterpret_cast<unsigned short*>(L_cur + a.block);   // [LW][block] the half-word indices, 16 bits each (the engine refuses node sets beyond 2^21 nodes)
+    u32* H_level = reinterpret_cast<u32*>(L_hw + (size_t)LW * a.block);   // R7 only: [block] the folded record's level ...
+    u32* H_meta = H_level + a.block;                                       // ... and its list length | R7M_* flags
     for (u32 j = tid; j < a.block; j += R6_COMMIT_THREADS) L_cur[j] = 0;
     for (u32 w = tid; w < (R7 ? tkw : Wn + VW); w += R6_COMMIT_THREADS) tk[w] = 0;
     for (u32 c = tid; c < n_rr; c += R6_COMMIT_THREADS) thr[c] = a.thr[c];
-    if (tid < 16) staged[tid] = 0;
-    // Wave v >= 1 applies the picks of the block's group v - 1 (tasks 64 (v - 1) ...) as soon as wave 0 has matched that group, while
-    // it matches the next ones; the task records are requested now. The groups no wave is left for (a block of more than 960 tasks)
-    // are applied by wave 0 behind its matching.
+    if (tid < 32) staged[tid] = 0;
+    // Wave v >= 1 applies the picks of the block's groups v - 1, v + 14, ... (group g: tasks 64 g ...) as soon as wave 0 has matched the
+    // group, while it matches the next ones; the first group's task records are requested now. (R7: a block has sixteen groups at most,
+    // and the last one is applied by wave 0 behind its matching.)
     const u32 wave_ = wv::wave();
-    const u32 mine = wave_ == 0 ? 15u * 64u + lane : (wave_ - 1u) * 64u + lane;   // the block-local task this thread applies
-    RTask r{};
-    if (mine < n) r = a.rt[pos + mine];
+    const u32 mine0 = wave_ == 0 ? (R7 ? 15u * 64u + lane : R6_NONE) : (wave_ - 1u) * 64u + lane;   // the first block-local task this thread applies
+    RTask r0{};
+    if (mine0 < n) r0 = a.rt[pos + mine0];
     if (tid == 0) { sh[3] = 0; sh[4] = 0; }
     if constexpr (R7 && CSI) {
         if (tid == 0) sh[12] = r7_take_trailers(a, m7, my, rnd);   // the volumes the other shards reserved in the round before: into this shard's table
@@ -765,23 +806,31 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             while (wv::lds_poll32(staged + (wave_ - fw)) == 0) wv::spin_pause();
         if ((tid & ~63u) < n) r7_fold_into(m7, tid < n ? tid : 0u, tid < n, a.block, L_hw, L_hb, H_level, H_meta, sh);   // (whole waves: it ballots)
     } else {
-        // (in group order, a few at a time — as the folds above: every wave's 64 uncoalesced loads per lane share the CU's one address path)
-        const u32 sw = ((a.dbg >> 8) & 15u) ? ((a.dbg >> 8) & 15u) : R6_STAGES_IN_FLIGHT;
-        if (wave_ >= sw)
-            while (wv::lds_poll32(staged + (wave_ - sw)) == 0) wv::spin_pause();
-        if (tid < n) {
+        // (waves 0 and 1: the block's first two groups, whose window is the front of the list; two waves' uncoalesced loads share the CU's
+        // one address path well — with all sixteen at it the matcher's own group queued behind the others')
+        if (wave_ < 2u && tid < n) {
             const R6Prop* q = a.prop + tid;
+            const u32 lv = q->level, nc = q->n_cand;
+            const u32 total = lv != R6_NONE ? (nc & 0x7FFFFFFFu) : 0u, cnt = min(total, win);
             const u32* qh = reinterpret_cast<const u32*>(q->hw);   // (two indices a dword)
-            for (int k = 0; k < R6_CAND; ++k) {
-                const u32 v = qh[k];
-                L_hw[(size_t)(2 * k) * a.block + tid] = (unsigned short)(v & 0xFFFFu);
-                L_hw[(size_t)(2 * k + 1) * a.block + tid] = (unsigned short)(v >> 16);
-            }
-            for (int k = 0; k < 2 * R6_CAND; ++k) L_hb[(size_t)k * a.block + tid] = q->hb[k];
+            u32 vh[LMAX / 2], vb[LMAX];   // (all requested together, whatever the list's length: a load under a predicate of its own waits for the one before it)
+            WV_UNROLL
+            for (int k = 0; k < (int)LMAX / 2; ++k) vh[k] = qh[k];
+            WV_UNROLL
+            for (int k = 0; k < (int)LMAX; ++k) vb[k] = q->hb[k];
+            WV_UNROLL
+            for (int k = 0; k < (int)LMAX; ++k)
+                if ((u32)k < win) {   // (behind the list's end: index 0 — the seating step reads an entry's TK word before it knows whether the entry counts)
+                    L_hw[(size_t)k * a.block + tid] = (u32)k < cnt ? (unsigned short)((k & 1) ? vh[k >> 1] >> 16 : vh[k >> 1] & 0xFFFFu) : (unsigned short)0;
+                    L_hb[(size_t)k * a.block + tid] = vb[k];
+                }
+            L_cur[tid] = (cnt << 8) | ((lv != R6_NONE && (total > cnt || (nc >> 31))) ? 0x10000u : 0u);
         }
     }
-    wv::lockstep();
-    if (lane == 0) wv::lds_publish32(staged + wave_, 1u);
+    if (R7 || wave_ < 2u) {
+        wv::lockstep();
+        if (lane == 0) wv::lds_publish32(staged + wave_, 1u);
+    }
     const u64 t1 = prof ? wv::clock64() : 0;
     u32 reseats = 0, seat_steps = 0;
     u64 cy_load = 0, cy_walk = 0, cy_g0 = 0, cy_g1 = 0, cy_g2 = 0;
@@ -823,15 +872,18 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 if (g0 + 128 < n) nx2 = head_of(i + 128 < n ? i + 128 : 0);
             }
             const u32 level = have ? p->level : 0u;
-            const u32 nent = (have && level != R6_NONE) ? (p->n_cand & 0x7FFFFFFFu) : 0u;
-            const bool plain = nent != 0;
+            const u32 lcur = have ? L_cur[i] : 0u;   // (the group's applying wave has skipped the dead entries so far)
+            // (a window may be empty — every entry was dead when it was staged — where the list is not: the task is still a plain one)
+            const u32 nent = R7 ? ((have && level != R6_NONE) ? (p->n_cand & 0x7FFFFFFFu) : 0u) : (lcur >> 8) & 0xFFu;
+            const bool plain = R7 ? nent != 0 : (have && level != R6_NONE);
+            const u32 left_out = R7 ? 0u : lcur >> 16;
             const bool exc = have && level == R6_NONE && p->exc_hi != KEY_NONE;
             const bool inf = have && level == R6_NONE && !exc;
             // Every lane carries two half-words of its list — the current one (bits, w) and the next one with a candidate left
             // (bits2, w2), which it steps to inside the walk — and a cursor behind them. An entry is looked at ONCE, against the TK
             // row as it is then (the picks of the earlier groups, and of this group's tasks in front of a stop): what it finds empty
             // stays empty, what it seats is struck by the walk from then on.
-            u32 bits = 0, w = 0, bits2 = 0, w2 = 0, cur = have ? L_cur[i] : 0u;   // (the group's applying wave has skipped the dead entries so far)
+            u32 bits = 0, w = 0, bits2 = 0, w2 = 0, cur = R7 ? lcur : lcur & 0xFFu;
             // (straight-line: every lane reads R6_SEAT entries — clamped to its list, the unused entries of a list are zero — and the TK
             // words behind them, the seats are filled by selects: a step is two LDS round trips and no divergent branch. An entry is
             // consumed while a seat is free; the first one that finds none stays for the next visit, and so do those behind it)
@@ -844,7 +896,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                     u32 h[R6_SEAT], b[R6_SEAT], t[R6_SEAT];
                     WV_UNROLL
                     for (int q = 0; q < R6_SEAT; ++q) {
-                        const u32 c = min(cur + (u32)q, 2u * R6_CAND - 1u);
+                        const u32 c = min(cur + (u32)q, win - 1u);
                         h[q] = L_hw[c * a.block + li];
                         b[q] = L_hb[c * a.block + li];
                     }
@@ -995,7 +1047,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                             if ((p->n_cand & 0x7FFFFFFFu) == 1) a.blk->dbg_cut[2] += 1;
                         }
                         cut = at;
-                        why = 1;
+                        why = wv::readlane(left_out, at) ? 4 : 1;   // (4: its window ran out, its list had more)
                         break;
                     }
                 }
@@ -1037,6 +1089,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             a.blk->rounds += 1;
             if (CPT && VW) a.blk->crounds += 1;   // a round with a compact index
             if (why == 1) a.blk->cut_exhausted += 1;
+            if (why == 4) a.blk->cut_window += 1;
             if (why == 2) a.blk->cut_exception += 1;
             if (why == 3) a.blk->cut_uncounted += 1;
             a.blk->reseats += reseats;   // (the host's sign of sparse lists: run_blocks switches the compact index on by it)
@@ -1054,33 +1107,8 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     }
     const u64 t2 = prof ? wv::clock64() : 0;
     const u32 base = a.blk->base;
-    // a wave waits (polling LDS, asleep in between) until its group is matched or the matching is over, and applies what was accepted of it
-    if (wave_ != 0) {
-        const u32 g0 = (wave_ - 1u) * 64u, need = min(g0 + 64u, n);
-        if (g0 > 0 && g0 < n)
-            while (wv::lds_poll32(staged + (g0 >> 6)) == 0) wv::spin_pause();
-        if (g0 > 0 && mine < n) {
-            // until the matcher reaches this wave's group: move every task's cursor over the entries that are dead by now (taken nodes
-            // stay taken: what is dead against an older TK row is dead), so that the matcher seats the group in a step or two
-            u32 lv = 0, nent = 0;
-            if constexpr (R7) { lv = H_level[mine]; nent = lv != R6_NONE ? (H_meta[mine] & 0xFFu) : 0u; }
-            else { lv = a.prop[mine].level; nent = lv != R6_NONE ? (a.prop[mine].n_cand & 0x7FFFFFFFu) : 0u; }
-            const u32* tk32 = reinterpret_cast<const u32*>(tk);
-            u32 cur = 0;
-            while (wv::lds_poll32(sh + 3) + 64u < g0 && wv::lds_poll32(sh + 4) == 0) {   // (stops a group early: the last value must be in LDS when it is read)
-                for (int q = 0; q < 4 && cur < nent; ++q) {
-                    if (L_hb[(size_t)cur * a.block + mine] & ~tk32[L_hw[(size_t)cur * a.block + mine]]) break;
-                    ++cur;
-                }
-                L_cur[mine] = cur;
-                wv::spin_pause();
-            }
-        }
-        if (g0 < n)
-            while (wv::lds_poll32(sh + 3) < need && wv::lds_poll32(sh + 4) == 0) wv::spin_pause();
-    }
-    const u32 acc_now = wv::readfirstlane(wv::lds_poll32(sh + 3));
-    if (mine < acc_now) {
+    // NodeInfo.addTask for the accepted pick of block-local task `mine` (record r): the node rows, the bitmaps, the commit log
+    auto apply = [&](const u32 mine, const RTask& r) {
         const u32 t = pos + mine, addr = pk_node[mine];
         u32 nd = addr;
         if (CPT) nd = addr == R6_NONE ? R6_NONE : addr < 64u * VW ? a.cidx[addr] : addr - 64u * VW;   // a compact position, or a node behind them
@@ -1154,6 +1182,150 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                     }
                 }
             }
+        }
+    };
+    if constexpr (R7) {
+        // a wave waits (polling LDS, asleep in between) until its group is matched or the matching is over, and applies what was accepted of it
+        if (wave_ != 0) {
+            const u32 g0 = (wave_ - 1u) * 64u, need = min(g0 + 64u, n);
+            if (g0 > 0 && g0 < n)
+                while (wv::lds_poll32(staged + (g0 >> 6)) == 0) wv::spin_pause();
+            if (g0 > 0 && mine0 < n) {
+                // until the matcher reaches this wave's group: move every task's cursor over the entries that are dead by now (taken nodes
+                // stay taken: what is dead against an older TK row is dead), so that the matcher seats the group in a step or two
+                const u32 lv = H_level[mine0], nent = lv != R6_NONE ? (H_meta[mine0] & 0xFFu) : 0u;
+                const u32* tk32 = reinterpret_cast<const u32*>(tk);
+                u32 cur = 0;
+                while (wv::lds_poll32(sh + 3) + 64u < g0 && wv::lds_poll32(sh + 4) == 0) {   // (stops a group early: the last value must be in LDS when it is read)
+                    for (int q = 0; q < 4 && cur < nent; ++q) {
+                        if (L_hb[(size_t)cur * a.block + mine0] & ~tk32[L_hw[(size_t)cur * a.block + mine0]]) break;
+                        ++cur;
+                    }
+                    L_cur[mine0] = cur;
+                    wv::spin_pause();
+                }
+            }
+            if (g0 < n)
+                while (wv::lds_poll32(sh + 3) < need && wv::lds_poll32(sh + 4) == 0) wv::spin_pause();
+        }
+        const u32 acc_now = wv::readfirstlane(wv::lds_poll32(sh + 3));
+        if (mine0 < acc_now) apply(mine0, r0);
+    } else if (wave_ != 0) {
+        // Helper h = wave - 1 takes the groups h, h + 15, ... in order: it stages the group's windows (g >= 2), moves the cursors over
+        // entries that die while the matcher works on the group before, waits for the group's picks and applies them. Every wait polls
+        // a word only wave 0 advances (sh[3]: tasks decided so far) and leaves when the matching is over (sh[4], read FIRST: sh[3] is
+        // final then); a helper that finds its group undecided at the end is done, the groups behind it are undecided as well.
+        const u32* tk32 = reinterpret_cast<const u32*>(tk);
+        RTask r = r0;
+        for (u32 g = wave_ - 1u; g * 64u < n; g += 15u) {
+            const u32 g0 = g * 64u, j = g0 + lane, need = min(g0 + 64u, n);
+            const bool have = j < n;
+            u32 cnt = 0, left = 0;
+            if (g >= 2u) {
+                const u32 jj = have ? j : 0u;
+                const R6Prop* q = a.prop + jj;
+                const R6PropExt* x = a.ext ? a.ext + jj : nullptr;
+                const u32 lv = q->level, nc = q->n_cand;
+                const u32 total = (have && lv != R6_NONE) ? (nc & 0x7FFFFFFFu) : 0u;   // (beyond 2 * R6_CAND only with an extension)
+                u32 at = 0;   // the entries in front of it are dead (whole batches of sixteen)
+                // The window from the TK row as it is: sixteen entries of the list at a time through registers, from `at` on, the live ones
+                // into the task's slot until it is full. `left`: the list goes on behind what was looked at, or behind the window.
+                auto stage = [&]() {
+                    cnt = 0;
+                    left = total ? nc >> 31 : 0u;
+                    bool lead = true;
+                    u32 p = at;
+                    while (p < total && cnt < win) {
+                        const u32* ph = p < 2u * R6_CAND ? reinterpret_cast<const u32*>(q->hw) + p / 2u : reinterpret_cast<const u32*>(x->hw) + (p - 2u * R6_CAND) / 2u;
+                        const u32* pb = p < 2u * R6_CAND ? q->hb + p : x->hb + (p - 2u * R6_CAND);
+                        u32 hwv[16], hbv[16], tkv[16];
+                        WV_UNROLL
+                        for (int k = 0; k < 8; ++k) {
+                            const u32 v = ph[k];
+                            hwv[2 * k] = v & 0xFFFFu;
+                            hwv[2 * k + 1] = v >> 16;
+                        }
+                        WV_UNROLL
+                        for (int k = 0; k < 16; ++k) hbv[k] = pb[k];
+                        WV_UNROLL
+                        for (int k = 0; k < 16; ++k) tkv[k] = tk32[p + (u32)k < total ? hwv[k] : 0u];   // (what lies behind the list's end is not an index)
+                        bool any = false;
+                        WV_UNROLL
+                        for (int k = 0; k < 16; ++k)
+                            if (p + (u32)k < total && (hbv[k] & ~tkv[k])) {
+                                any = true;
+                                if (cnt < win) {
+                                    L_hw[(size_t)cnt * a.block + j] = (unsigned short)hwv[k];
+                                    L_hb[(size_t)cnt * a.block + j] = hbv[k];
+                                    ++cnt;
+                                } else
+                                    left = 1;
+                            }
+                        p += 16u;
+                        if (lead && !any && p < total) at = p;
+                        else lead = false;
+                    }
+                    if (p < total) left = 1;
+                    if (have) {
+                        for (u32 k = cnt; k < win; ++k) L_hw[(size_t)k * a.block + j] = 0;   // (as the prologue's: a valid TK word behind every entry the seating step may read)
+                        L_cur[j] = (cnt << 8) | (left << 16);
+                    }
+                };
+                // Taken nodes stay taken, so a window staged against an older TK row holds nothing wrong, only entries that may have died
+                // since (the cursor loop and the seating step meet those): the slot is staged again whenever the matcher publishes a group,
+                // loads and all, while there is time — when the picks of group g - 2 are out it is ready but for that group's picks, and is
+                // published at once: no load between the matcher and the group. (A helper that comes late stages then.)
+                // Only the helpers of the next few groups do so: the uncoalesced loads of many waves queue up in the CU's one address path,
+                // in front of the matcher's own (all helpers at once at the kernel's start: 15 k cycles of every round's prologue).
+                // (Windows of 2 * R6_CAND rows — batches of runs, whose groups the matcher is through in a few thousand cycles: nothing to
+                // wait for, a window is the front of the list. Staged right away, two groups at a time in group order as the prologue's —
+                // the one wait in this kernel on a word a HELPER advances (staged[g - 2]): staging there depends on nothing the matcher
+                // does, so the chain g - 2, g - 4, ... ends at the prologue's two groups; it leaves on sh[4] like every other.)
+                u32 seen = 0;
+                bool fresh = false;
+                if (LW == LMAX) {
+                    for (;;) {
+                        const bool over = wv::lds_poll32(sh + 4) != 0;
+                        if (wv::lds_poll32(staged + (g - 2u)) != 0 || over) break;
+                        wv::spin_pause();
+                    }
+                    stage();
+                    fresh = true;
+                }
+                for (;;) {
+                    const bool over = wv::lds_poll32(sh + 4) != 0;
+                    const u32 acc = wv::lds_poll32(sh + 3);
+                    if (acc + 64u >= g0 || over || LW == LMAX) break;
+                    if (acc != seen && acc + 192u >= g0) {
+                        seen = acc;
+                        stage();
+                        fresh = true;
+                    }
+                    wv::spin_pause();
+                }
+                if (LW != LMAX && wv::lds_poll32(sh + 3) + 64u < g0) break;   // (over: the block was cut in front of group g - 1)
+                if (!fresh) stage();
+                wv::lockstep();
+                if (lane == 0) wv::lds_publish32(staged + g, 1u);
+            }
+            if (g >= 15u && have) r = a.rt[pos + j];   // (the first group's record was requested in the prologue)
+            u32 cur = 0;
+            for (;;) {
+                const bool over = wv::lds_poll32(sh + 4) != 0;
+                const u32 acc = wv::lds_poll32(sh + 3);
+                if (acc >= need || over) break;
+                if (g >= 2u && have && acc < g0) {   // (the matcher reads the cursor when it starts on the group; a later value is lost, no harm)
+                    for (int q = 0; q < 4 && cur < cnt; ++q) {
+                        if (L_hb[(size_t)cur * a.block + j] & ~tk32[L_hw[(size_t)cur * a.block + j]]) break;
+                        ++cur;
+                    }
+                    L_cur[j] = cur | (cnt << 8) | (left << 16);
+                }
+                wv::spin_pause();
+            }
+            const u32 acc_now = wv::readfirstlane(wv::lds_poll32(sh + 3));
+            if (j < acc_now) apply(j, r);
+            if (acc_now < need) break;
         }
     }
     if (prof && wave_ == 1 && lane == 0) a.blk->cyc[3] += (u32)((wv::clock64() - t2) >> 6);   // the first group's applying wave: waiting for it + applying

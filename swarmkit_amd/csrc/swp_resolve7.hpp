@@ -62,7 +62,7 @@ struct R7Args {
 
 // TK row over the padded half-word space, thresholds, the block's picks / cursors / lists / folded heads (r6_commit_t's LDS, instance R7)
 inline __host__ __device__ size_t r7_commit_lds(u32 hw_total, u32 block, u32 n_rr) {
-    return (size_t)((hw_total + 1) / 2 + n_rr) * 8 + (size_t)block * (16 + 2 * R6_CAND * 6 + 8) + 128;
+    return (size_t)((hw_total + 1) / 2 + n_rr) * 8 + (size_t)block * (16 + 2 * R6_CAND * 6 + 8) + 192;
 }
 
 #ifdef SWP_R6_KERNELS
