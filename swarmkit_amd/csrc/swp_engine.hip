@@ -1785,6 +1785,7 @@ int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_row
     ra.task_rows = r6_task_rows ? 1u : 0u;
     ra.trows = r6_task_rows ? b->d_trows.as<u64>() : nullptr;
     ra.dbg = dbg_bits;
+    ra.no_runs = b->tasks_in_runs == 0 ? 1u : 0u;   // (round-robin batches: nothing for the matcher's runs-by-rank path to find)
     ra.valid = e->d_valid.as<u64>();
     ra.sc = b->d_sc.as<u64>();
     ra.X = b->d_X.as<u64>();
@@ -2121,6 +2122,8 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
                     hb.cyc[0] * 64.0 / rr_, hb.cyc[1] * 64.0 / rr_, hb.cyc_load * 64.0 / rr_, hb.cyc_walk * 64.0 / rr_, hb.cyc[2] * 64.0 / rr_, hb.cyc[3] * 64.0 / rr_, hb.reseats / rr_);
             fprintf(stderr, "[swp] ... of the list loads: waiting for a group's lists %.0f, its head records %.0f, seating %.0f (%.1f steps of the seating loop, stops included) per round\n", hb.cyc_g[0] * 64.0 / rr_,
                     hb.cyc_g[1] * 64.0 / rr_, hb.cyc_g[2] * 64.0 / rr_, hb.cyc_g[3] / rr_);
+            fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hb.cyc_h[0] * 64.0 / rr_, hb.cyc_h[1] * 64.0 / rr_,
+                    hb.cyc_h[2] * 64.0 / rr_);
         }
         return SWP_OK;
     };
@@ -4172,6 +4175,8 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
                 hh.cyc[0] * 64.0 / rr_, hh.cyc[1] * 64.0 / rr_, hh.cyc_load * 64.0 / rr_, hh.cyc_walk * 64.0 / rr_, hh.cyc[3] * 64.0 / rr_, hh.reseats / rr_);
         fprintf(stderr, "[swp] ... of the list loads: waiting for a group's lists %.0f, its head records %.0f, seating %.0f (%.1f steps of the seating loop, stops included) per round\n", hh.cyc_g[0] * 64.0 / rr_,
                 hh.cyc_g[1] * 64.0 / rr_, hh.cyc_g[2] * 64.0 / rr_, hh.cyc_g[3] / rr_);
+        fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hh.cyc_h[0] * 64.0 / rr_, hh.cyc_h[1] * 64.0 / rr_,
+                hh.cyc_h[2] * 64.0 / rr_);
     }
     cleanup();
     return SWP_OK;

@@ -73,8 +73,10 @@ struct Blk6 {   // control block, global memory
     u32 scan_batches;      // k_scanb: barriers it took for the tasks it did look at
     u32 cut_window;        // cuts in front of a task whose LDS window ran out while something lay behind it: live entries, entries nobody looked at
                            // (possibly dead), or more of the level than was listed (bit 31) — an upper bound of the cuts a whole list would have avoided; not in cut_exhausted
+    u32 cyc_h[3];          // dbg: cyc_g[1] split — up to the first use of the head record / template id, the flags and the cursor from LDS, the run path
+    u32 dbg_late_runs;     // dbg: tasks whose pick the runs-by-rank path took in a group >= 2 (descriptor ids a helper left in the group's pick slots)
 };
-static_assert(sizeof(Blk6) == 116, "Blk6 layout");
+static_assert(sizeof(Blk6) == 132, "Blk6 layout");
 
 struct R6Prop {   // one task's proposal: the shard protocol's record (include/swp.h swp_proposal) with more candidates, as 32-node half-words
     u32 level, n_cand;       // minimum level among the plain candidates (R6_NONE: there is none); half-words listed | bit 31: there are more
@@ -166,12 +168,26 @@ struct R6Args {
     // [block] the list entries beyond the proposal's; nullptr: lists end with the proposal (the shard drivers: the record they exchange)
     R6PropExt* ext;
     u32 win;                 // list entries a task in the commit kernel's LDS (r6_win_of: 0 = R6_WIN); the launch sizes the LDS by it
+    u32 no_runs;             // != 0: the batch has no run of >= 8 consecutive identical tasks (counted when it is built): the matcher leaves the
+                             // runs-by-rank path and the descriptor ids it reads alone (its entry found nothing in every group of the headline:
+                             // 4 650 of a round's 160 k cycles)
 };
 struct R7Args;   // swp_resolve7.hpp: what a shard's commit kernel knows of the other shards
 #define R7_FOLDS_IN_FLIGHT 4u   // waves that fold at the same time (the R7 staging below); SWP_DBG bits 8-11 override it for A/B runs (tools/gpu_r5_foldwin.sh)
 #define R7M_EXC 0x100u   // H_meta of a folded record: list length | the task has an exception-list candidate on some shard | it does not count on its node | it has cluster mounts
 #define R7M_UNC 0x200u
 #define R7M_CSI 0x400u
+// A task's L_cur word in the single engine's commit kernel (not R7): cursor | entries in the window << 8 | the bits below. The wave that
+// stages the task's window holds its record: it leaves what the matcher needs of the record's head here, so that wave 0 reads a group's
+// set-up from LDS only. Every writer of the word carries them (the prologue, a helper's stage() and its cursor loop).
+#define R6C_LEFT 0x10000u     // something of the list was left out of the window
+#define R6C_PLAIN 0x20000u    // level != R6_NONE: the task has plain candidates
+#define R6C_EXC 0x40000u      // exc_hi != KEY_NONE: its service's exception list has a candidate
+#define R6C_UNC 0x80000u      // flags bit 0: it does not count on its node
+#define R6C_CSI 0x100000u     // flags bit 1: it has cluster mounts
+inline __host__ __device__ u32 r6_head_bits(u32 level, u64 exc_hi, u32 flags) {
+    return (level != R6_NONE ? R6C_PLAIN : 0u) | (exc_hi != KEY_NONE ? R6C_EXC : 0u) | ((flags & 1u) ? R6C_UNC : 0u) | ((flags & 2u) ? R6C_CSI : 0u);
+}
 
 #define R6_UNROLL 4              // 64-word chunks a propose wave has in flight together ...
 #define R6_SMALL_WORDS 512u      // ... on node sets beyond this many words (32 768 nodes); up to there a wave has ONE chunk: a quarter of the registers, so that
@@ -771,7 +787,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     const u32 win = (R7 || !((a.dbg >> 12) & 31u)) ? LW : min((a.dbg >> 12) & 31u, LW);   // (dbg bits 12-16: a shorter window, tests)
     u32* L_hb = sh + 48;                                         // [LW][block] entry-major: lane i of the matcher reads
     u32* L_cur = L_hb + (size_t)LW * a.block;                    // ... entry k of task i at [k * block + i] (no bank conflicts); [block] a lower bound of every task's cursor: the entries in front of it are dead
-                                                                 // (not R7: | entries in the window << 8 | something was left out of it << 16)
+                                                                 // (not R7: | entries in the window << 8 | R6C_LEFT | the head's bits, R6C_*)
     unsigned short* L_hw = reinterpret_cast<unsigned short*>(L_cur + a.block);   // [LW][block] the half-word indices, 16 bits each (the engine refuses node sets beyond 2^21 nodes)
     u32* H_level = reinterpret_cast<u32*>(L_hw + (size_t)LW * a.block);   // R7 only: [block] the folded record's level ...
     u32* H_meta = H_level + a.block;                                       // ... and its list length | R7M_* flags
@@ -792,6 +808,9 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     }
     const bool prof = (a.dbg & 16u) != 0;
     const u64 t0 = prof ? wv::clock64() : 0;
+    const bool runs_on = !R7 && a.tmpl != nullptr && a.no_runs == 0;   // the runs-by-rank path below
+    u64 exc0_lo = 0;      // thread 0: the exception-list candidate of the block's first task, the only one that may use its own
+    u32 exc0_entry = 0;
     wv::barrier();
     // every thread stages the lists of its task (wave g: the block's group g): the matcher walks them with a cursor (an entry is looked
     // at once) instead of holding all of them in registers. No barrier: a group's flag is published when its lists are in LDS.
@@ -810,7 +829,13 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
         // one address path well — with all sixteen at it the matcher's own group queued behind the others')
         if (wave_ < 2u && tid < n) {
             const R6Prop* q = a.prop + tid;
-            const u32 lv = q->level, nc = q->n_cand;
+            const u32 lv = q->level, nc = q->n_cand, fl = q->flags;
+            const u64 xh = q->exc_hi;
+            const u32 tm = runs_on ? a.tmpl[pos + tid] : 0u;
+            if (tid == 0) {
+                exc0_lo = q->exc_lo;
+                exc0_entry = q->exc_entry;
+            }
             const u32 total = lv != R6_NONE ? (nc & 0x7FFFFFFFu) : 0u, cnt = min(total, win);
             const u32* qh = reinterpret_cast<const u32*>(q->hw);   // (two indices a dword)
             u32 vh[LMAX / 2], vb[LMAX];   // (all requested together, whatever the list's length: a load under a predicate of its own waits for the one before it)
@@ -824,7 +849,8 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                     L_hw[(size_t)k * a.block + tid] = (u32)k < cnt ? (unsigned short)((k & 1) ? vh[k >> 1] >> 16 : vh[k >> 1] & 0xFFFFu) : (unsigned short)0;
                     L_hb[(size_t)k * a.block + tid] = vb[k];
                 }
-            L_cur[tid] = (cnt << 8) | ((lv != R6_NONE && (total > cnt || (nc >> 31))) ? 0x10000u : 0u);
+            L_cur[tid] = (cnt << 8) | ((lv != R6_NONE && (total > cnt || (nc >> 31))) ? R6C_LEFT : 0u) | r6_head_bits(lv, xh, fl);
+            if (runs_on) pk_idx[tid] = tm;   // the task's descriptor id, in its own pick slot: nobody reads the slot before the group is matched
         }
     }
     if (R7 || wave_ < 2u) {
@@ -832,53 +858,49 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
         if (lane == 0) wv::lds_publish32(staged + wave_, 1u);
     }
     const u64 t1 = prof ? wv::clock64() : 0;
-    u32 reseats = 0, seat_steps = 0;
-    u64 cy_load = 0, cy_walk = 0, cy_g0 = 0, cy_g1 = 0, cy_g2 = 0;
+    u32 reseats = 0, seat_steps = 0, late_runs = 0;
+    u64 cy_load = 0, cy_walk = 0, cy_g0 = 0, cy_g1 = 0, cy_g2 = 0, cy_h0 = 0, cy_h1 = 0, cy_h2 = 0;
     if (wave_ == 0) {
         u32 nc = a.ctl->ncommit, ni = a.ctl->ninf, acc = 0, why = 0;
         u32* tk32 = reinterpret_cast<u32*>(tk);   // the same row as 32-node half-words
         bool stop = false, csi_seen = false;   // csi_seen: a task with cluster mounts is decided in this block already
-        // the scalar part of a task's record (level, list length, exception-list candidate); the next group's is in flight while a group is matched
-        struct Head { u32 level, n_cand; u64 exc_hi, exc_lo; u32 exc_entry, flags; };
-        auto head_of = [&](u32 j) {
-            const R6Prop* q = a.prop + j;
-            return Head{q->level, q->n_cand, q->exc_hi, q->exc_lo, q->exc_entry, q->flags};
-        };
-        // (R7: the folded heads are in LDS once the group is staged — read behind the wait below; only the block's first task may use its
-        // exception-list candidate, whose record its staging thread left in sh[8..10])
+        // The scalar part of a task's record (level, list length, exception-list candidate, flags) comes from LDS once the group is staged,
+        // read behind the wait below: the staging wave left it in the task's L_cur word (R6C_*) and, the descriptor id, in its pk_idx
+        // slot — no global load between two walks. (Until the heads moved there wave 0 requested every group's records itself, two groups
+        // ahead: six uncoalesced loads a lane in the CU's one address path, next to the helpers' staging loads.)
+        // (R7: the folded heads; only the block's first task may use its exception-list candidate, whose record its staging thread left
+        // in sh[8..10] — the single engine's thread 0 keeps it from its prologue load)
+        struct Head { u32 level, n_cand; u64 exc_hi; u32 flags; };
         auto head7 = [&](u32 j) {
             const u32 mt = H_meta[j];
-            return Head{H_level[j], mt & 0xFFu, (mt & R7M_EXC) ? 0ull : KEY_NONE, 0ull, 0u, ((mt & R7M_UNC) ? 1u : 0u) | ((mt & R7M_CSI) ? 2u : 0u)};
+            return Head{H_level[j], mt & 0xFFu, (mt & R7M_EXC) ? 0ull : KEY_NONE, ((mt & R7M_UNC) ? 1u : 0u) | ((mt & R7M_CSI) ? 2u : 0u)};
         };
-        Head nxt{}, nx2{};   // the heads of the next group and of the one behind it (a group that is one run of identical tasks is through
-                              // before a load issued at its start has answered: two groups ahead since round 6)
-        if constexpr (!R7) {
-            nxt = head_of(lane < n ? lane : 0);
-            nx2 = head_of(64u + lane < n ? 64u + lane : 0);
-        }
         if (R7 && CSI && sh[12]) csi_seen = true;   // a reservation arrived from another shard only now: the proposals of tasks with mounts were made without it
         for (u32 g0 = 0; g0 < n && !stop; g0 += 64) {
             const u32 i = g0 + lane, glim = min(64u, n - g0);
             const bool have = i < n;
-            const u32 tmid = (!R7 && a.tmpl != nullptr && have) ? a.tmpl[pos + i] : 0u;   // the task's descriptor id (a RUN of identical tasks: below); requested ahead of the wait
             const u64 tg0 = prof ? wv::clock64() : 0;
             while (wv::lds_poll32(staged + (g0 >> 6)) == 0) wv::spin_pause();   // (long there, but for the first groups of a block)
             const u64 tga = prof ? wv::clock64() : 0;
-            Head rec = nxt;
-            if constexpr (R7) rec = head7(have ? i : 0u);
-            const Head* p = &rec;
-            if constexpr (!R7) {
-                nxt = nx2;
-                if (g0 + 128 < n) nx2 = head_of(i + 128 < n ? i + 128 : 0);
-            }
-            const u32 level = have ? p->level : 0u;
             const u32 lcur = have ? L_cur[i] : 0u;   // (the group's applying wave has skipped the dead entries so far)
+            // the task's descriptor id (a RUN of identical tasks: below) — in a register before the run path uses the group's pick slots as scratch
+            const u32 tmid = (runs_on && have) ? pk_idx[i] : 0u;
+            if (prof) wv::keep(lcur ^ tmid);   // (the timer below: behind the wait for both)
+            const u64 th0 = prof ? wv::clock64() : 0;
             // (a window may be empty — every entry was dead when it was staged — where the list is not: the task is still a plain one)
-            const u32 nent = R7 ? ((have && level != R6_NONE) ? (p->n_cand & 0x7FFFFFFFu) : 0u) : (lcur >> 8) & 0xFFu;
-            const bool plain = R7 ? nent != 0 : (have && level != R6_NONE);
-            const u32 left_out = R7 ? 0u : lcur >> 16;
-            const bool exc = have && level == R6_NONE && p->exc_hi != KEY_NONE;
-            const bool inf = have && level == R6_NONE && !exc;
+            u32 nent = (lcur >> 8) & 0xFFu, tflags = (lcur / R6C_UNC) & 3u;   // tflags: R6Prop.flags
+            bool plain = (lcur & R6C_PLAIN) != 0;
+            bool exc = !plain && (lcur & R6C_EXC) != 0;
+            const u32 left_out = R7 ? 0u : (lcur / R6C_LEFT) & 1u;
+            if constexpr (R7) {
+                const Head rec = head7(have ? i : 0u);
+                const u32 level = have ? rec.level : 0u;
+                nent = (have && level != R6_NONE) ? (rec.n_cand & 0x7FFFFFFFu) : 0u;
+                plain = nent != 0;
+                exc = have && level == R6_NONE && rec.exc_hi != KEY_NONE;
+                tflags = rec.flags;
+            }
+            const bool inf = have && !plain && !exc;
             // Every lane carries two half-words of its list — the current one (bits, w) and the next one with a candidate left
             // (bits2, w2), which it steps to inside the walk — and a cursor behind them. An entry is looked at ONCE, against the TK
             // row as it is then (the picks of the earlier groups, and of this group's tasks in front of a stop): what it finds empty
@@ -929,11 +951,13 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             // (A group usually holds the end of one service's run and the start of the next: up to eight runs — or stretches of a run that
             // one list's free candidates cover — in front of the group's first task that is not plain-and-counted are taken this way, one after the other — a run's picks are in the TK row before the
             // next run counts; the lanes behind them are seated and walked as ever, from there.)
+            if (prof) wv::keep(cur ^ (u32)inf);   // (the timer below: behind the LDS reads)
+            const u64 th1 = prof ? wv::clock64() : 0;
             u32 fdone = 0;   // lanes [0, fdone) have their picks from the run path
             u32 fr_w = 0, fr_b = 0;
             if constexpr (!R7) {
-                if (a.tmpl != nullptr && g0 + 64u <= a.block) {   // (the scratch below: 64 pick slots from g0 on)
-                    const bool simple = have && plain && !(p->flags & 3u);
+                if (runs_on && g0 + 64u <= a.block) {   // (the scratch below: 64 pick slots from g0 on)
+                    const bool simple = have && plain && !(tflags & 3u);
                     const u64 ns = ~wv::ballot(simple);
                     const u32 nsimple = min(glim, ns ? (u32)wv::ffs64(ns) : 64u);
                     for (u32 it = 0; it < 8u && fdone + 8u <= nsimple; ++it) {
@@ -986,11 +1010,12 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 }
             }
             const u64 tgb = prof ? wv::clock64() : 0;
+            if (prof && g0 >= 128u) late_runs += fdone;   // (reported with the timers)
             if (fdone < glim) seat(plain && lane >= fdone, 1u);   // (a second optional step costs more than the stops it saves)
             const u64 tgc = prof ? wv::clock64() : 0;
-            if (prof) { cy_g0 += tga - tg0; cy_g1 += tgb - tga; cy_g2 += tgc - tgb; }
+            if (prof) { cy_g0 += tga - tg0; cy_g1 += tgb - tga; cy_g2 += tgc - tgb; cy_h0 += th0 - tga; cy_h1 += th1 - th0; cy_h2 += tgb - th1; }
             const u64 lanes = glim == 64 ? ~0ull : (1ull << glim) - 1ull;
-            const u64 m_plain = wv::ballot(plain), m_inf = wv::ballot(inf), m_exc = wv::ballot(exc), m_unc = wv::ballot(plain && (p->flags & 1u));
+            const u64 m_plain = wv::ballot(plain), m_inf = wv::ballot(inf), m_exc = wv::ballot(exc), m_unc = wv::ballot(plain && (tflags & 1u));
             // the group ends in front of a task that must use its exception list (its order moves with every placement of the service:
             // only a block's first task may) and behind an uncounted task (its node stays on its level: the later lists are stale about it)
             u32 cut = glim;
@@ -998,7 +1023,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             if (m_exc) { cut = (u32)wv::ffs64(m_exc); why = 2; }
             if (m_unc && (u32)wv::ffs64(m_unc) < cut) { cut = (u32)wv::ffs64(m_unc) + 1; why = 3; last = true; }
             {   // tasks with cluster mounts: the block's first one is decided, the block is cut in front of the next (their lists know nothing of each other's volumes)
-                const u64 all_csi = wv::ballot(have && (p->flags & 2u));
+                const u64 all_csi = wv::ballot(have && (tflags & 2u));
                 u64 m_csi = all_csi;
                 if (m_csi && !csi_seen) m_csi &= m_csi - 1ull;   // (the first one of the block stays)
                 if (m_csi && (u32)wv::ffs64(m_csi) < cut) { cut = (u32)wv::ffs64(m_csi); why = 2; last = false; }
@@ -1007,9 +1032,9 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             u32 m_pick = R6_NONE;
             if (g0 == 0 && (m_exc & 1ull)) {   // the block's first task, from its exception list; the block ends behind it
                 if (lane == 0) {
-                    pk_node[0] = (u32)p->exc_lo + 64u * VW;   // (an address, like the matcher's picks)
+                    pk_node[0] = (u32)exc0_lo + 64u * VW;   // (an address, like the matcher's picks)
                     pk_idx[0] = nc;
-                    pk_aux[0] = p->exc_entry;
+                    pk_aux[0] = exc0_entry;
                     if constexpr (R7) {
                         pk_node[0] = r7_addr(m7, sh[8], sh[9]);
                         pk_aux[0] = sh[10];
@@ -1041,10 +1066,11 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 {
                     seat(served && lane >= at, 1u);
                     if (wv::readlane(bits, at) == 0) {   // every listed node is taken: propose again against the new state
-                        if (prof && lane == at) {
-                            if (p->n_cand >> 31) a.blk->dbg_cut[0] += 1;
+                        if (prof && lane == at) {   // (off the production path: the list's length from the record itself)
+                            const u32 ncd = R7 ? H_meta[li] & 0xFFu : a.prop[li].n_cand;
+                            if (ncd >> 31) a.blk->dbg_cut[0] += 1;
                             if (CPT && L_hw[li] < 2u * VW) a.blk->dbg_cut[1] += 1;
-                            if ((p->n_cand & 0x7FFFFFFFu) == 1) a.blk->dbg_cut[2] += 1;
+                            if ((ncd & 0x7FFFFFFFu) == 1) a.blk->dbg_cut[2] += 1;
                         }
                         cut = at;
                         why = wv::readlane(left_out, at) ? 4 : 1;   // (4: its window ran out, its list had more)
@@ -1102,6 +1128,10 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 a.blk->cyc_g[1] += (u32)(cy_g1 >> 6);
                 a.blk->cyc_g[2] += (u32)(cy_g2 >> 6);
                 a.blk->cyc_g[3] += seat_steps;
+                a.blk->cyc_h[0] += (u32)(cy_h0 >> 6);
+                a.blk->cyc_h[1] += (u32)(cy_h1 >> 6);
+                a.blk->cyc_h[2] += (u32)(cy_h2 >> 6);
+                a.blk->dbg_late_runs += late_runs;
             }
         }
     }
@@ -1220,12 +1250,14 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
         for (u32 g = wave_ - 1u; g * 64u < n; g += 15u) {
             const u32 g0 = g * 64u, j = g0 + lane, need = min(g0 + 64u, n);
             const bool have = j < n;
-            u32 cnt = 0, left = 0;
+            u32 cnt = 0, left = 0, hbits = 0;   // hbits: the head's bits of the task's L_cur word
             if (g >= 2u) {
                 const u32 jj = have ? j : 0u;
                 const R6Prop* q = a.prop + jj;
                 const R6PropExt* x = a.ext ? a.ext + jj : nullptr;
                 const u32 lv = q->level, nc = q->n_cand;
+                hbits = r6_head_bits(lv, q->exc_hi, q->flags);
+                if (runs_on && have) pk_idx[j] = a.tmpl[pos + j];   // (this wave applied the group fifteen in front of this one before it came here: other slots)
                 const u32 total = (have && lv != R6_NONE) ? (nc & 0x7FFFFFFFu) : 0u;   // (beyond 2 * R6_CAND only with an extension)
                 u32 at = 0;   // the entries in front of it are dead (whole batches of sixteen)
                 // The window from the TK row as it is: sixteen entries of the list at a time through registers, from `at` on, the live ones
@@ -1268,7 +1300,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                     if (p < total) left = 1;
                     if (have) {
                         for (u32 k = cnt; k < win; ++k) L_hw[(size_t)k * a.block + j] = 0;   // (as the prologue's: a valid TK word behind every entry the seating step may read)
-                        L_cur[j] = (cnt << 8) | (left << 16);
+                        L_cur[j] = (cnt << 8) | (left << 16) | hbits;
                     }
                 };
                 // Taken nodes stay taken, so a window staged against an older TK row holds nothing wrong, only entries that may have died
@@ -1319,7 +1351,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                         if (L_hb[(size_t)cur * a.block + j] & ~tk32[L_hw[(size_t)cur * a.block + j]]) break;
                         ++cur;
                     }
-                    L_cur[j] = cur | (cnt << 8) | (left << 16);
+                    L_cur[j] = cur | (cnt << 8) | (left << 16) | hbits;
                 }
                 wv::spin_pause();
             }
