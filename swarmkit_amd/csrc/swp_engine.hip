@@ -2124,6 +2124,8 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
                     hb.cyc_g[1] * 64.0 / rr_, hb.cyc_g[2] * 64.0 / rr_, hb.cyc_g[3] / rr_);
             fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hb.cyc_h[0] * 64.0 / rr_, hb.cyc_h[1] * 64.0 / rr_,
                     hb.cyc_h[2] * 64.0 / rr_);
+            fprintf(stderr, "[swp] ... of the walks and behind them: inside the walk %.0f (%.1f calls), the stops %.0f, a group's epilogue (last walk to publish) %.0f per round\n", hb.cyc_s[0] * 64.0 / rr_, hb.dbg_walks / rr_,
+                    hb.cyc_s[1] * 64.0 / rr_, hb.cyc_s[2] * 64.0 / rr_);
         }
         return SWP_OK;
     };
@@ -4177,6 +4179,8 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
                 hh.cyc_g[1] * 64.0 / rr_, hh.cyc_g[2] * 64.0 / rr_, hh.cyc_g[3] / rr_);
         fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hh.cyc_h[0] * 64.0 / rr_, hh.cyc_h[1] * 64.0 / rr_,
                 hh.cyc_h[2] * 64.0 / rr_);
+        fprintf(stderr, "[swp] ... of the walks and behind them: inside the walk %.0f (%.1f calls), the stops %.0f, a group's epilogue (last walk to publish) %.0f per round\n", hh.cyc_s[0] * 64.0 / rr_, hh.dbg_walks / rr_,
+                hh.cyc_s[1] * 64.0 / rr_, hh.cyc_s[2] * 64.0 / rr_);
     }
     cleanup();
     return SWP_OK;

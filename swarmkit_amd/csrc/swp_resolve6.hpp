@@ -50,6 +50,17 @@ namespace swpdev {
 #define R6_CAND 16               // a proposal lists 2 * R6_CAND non-empty 32-node half-words: a block is cut where a task finds all its listed nodes taken
 #endif
 #define R6_SEAT 2                 // list entries a seating step of the matcher looks at (4 measured no better: fewer steps, each longer)
+#ifndef R6_SEAT_AHEAD
+#define R6_SEAT_AHEAD 1          // the matcher requests the entries at a lane's cursor when the cursor moves, not when it stops there (0: at the stop — A/B builds, tests/emu)
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define R6_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)   // the instruction scheduler moves nothing across this point (not a memory fence, no instruction)
+#else
+#define R6_SCHED_FENCE() ((void)0)
+#endif
+#ifndef R6_REACH
+#define R6_REACH(what, cond)     // tests/emu counts the paths of the matcher a run came across (a driver defines it in front of this header); nothing in the product
+#endif
 #define R6_BMAX 2048             // largest block of a single engine (waves 1..15 of the commit kernel apply its 64-task groups in turn)
 #define R7_BMAX 1024             // ... of the node-range shards: one group per wave of their commit kernel
 #define R6_COMMIT_THREADS 1024
@@ -75,8 +86,11 @@ struct Blk6 {   // control block, global memory
                            // (possibly dead), or more of the level than was listed (bit 31) — an upper bound of the cuts a whole list would have avoided; not in cut_exhausted
     u32 cyc_h[3];          // dbg: cyc_g[1] split — up to the first use of the head record / template id, the flags and the cursor from LDS, the run path
     u32 dbg_late_runs;     // dbg: tasks whose pick the runs-by-rank path took in a group >= 2 (descriptor ids a helper left in the group's pick slots)
+    u32 cyc_s[3];          // dbg: cyc_walk split (and what follows it) — inside wv::match_seq64, the stops (a walk's return to the next walk's entry, or to
+                           // the cut at an exhausted list), a group's epilogue (its last walk's end to the publish of its picks)
+    u32 dbg_walks;         // dbg: calls of wv::match_seq64
 };
-static_assert(sizeof(Blk6) == 132, "Blk6 layout");
+static_assert(sizeof(Blk6) == 148, "Blk6 layout");
 
 struct R6Prop {   // one task's proposal: the shard protocol's record (include/swp.h swp_proposal) with more candidates, as 32-node half-words
     u32 level, n_cand;       // minimum level among the plain candidates (R6_NONE: there is none); half-words listed | bit 31: there are more
@@ -859,7 +873,8 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     }
     const u64 t1 = prof ? wv::clock64() : 0;
     u32 reseats = 0, seat_steps = 0, late_runs = 0;
-    u64 cy_load = 0, cy_walk = 0, cy_g0 = 0, cy_g1 = 0, cy_g2 = 0, cy_h0 = 0, cy_h1 = 0, cy_h2 = 0;
+    u64 cy_load = 0, cy_walk = 0, cy_g0 = 0, cy_g1 = 0, cy_g2 = 0, cy_h0 = 0, cy_h1 = 0, cy_h2 = 0, cy_s0 = 0, cy_s1 = 0, cy_s2 = 0;
+    u32 walks = 0;
     if (wave_ == 0) {
         u32 nc = a.ctl->ncommit, ni = a.ctl->ninf, acc = 0, why = 0;
         u32* tk32 = reinterpret_cast<u32*>(tk);   // the same row as 32-node half-words
@@ -907,20 +922,47 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             // stays empty, what it seats is struck by the walk from then on.
             u32 bits = 0, w = 0, bits2 = 0, w2 = 0, cur = R7 ? lcur : lcur & 0xFFu;
             // (straight-line: every lane reads R6_SEAT entries — clamped to its list, the unused entries of a list are zero — and the TK
-            // words behind them, the seats are filled by selects: a step is two LDS round trips and no divergent branch. An entry is
+            // words behind them, the seats are filled by selects: a step is two LDS round trips — one with R6_SEAT_AHEAD, below — and no divergent branch. An entry is
             // consumed while a seat is free; the first one that finds none stays for the next visit, and so do those behind it)
             const u32 li = have ? i : 0u;
-            auto seat = [&](bool want, u32 opt_steps) {   // lanes with `want` fill their free seats from their cursor on
-                for (u32 step = 0;; ++step) {   // (after opt_steps steps: only as long as a lane has NO seat)
-                    const bool go = want && bits2 == 0 && cur < nent;
-                    if (!(step < opt_steps ? wv::ballot(go) : wv::ballot(go && bits == 0))) break;
+            // R6_SEAT_AHEAD: the entries at the cursor (ah, ab) are requested whenever the cursor has a new value — behind the group's
+            // L_cur word and at the end of every seating step — and not waited for: they are in their registers by the time the walk
+            // stops, so a stop starts with the TK reads, issued right behind its flush (one LDS round trip of a lone wave among sixteen
+            // instead of two, and no address arithmetic). What is read early is what would be read at the stop:
+            //   * `cur` moves only in the seating step, which requests the entries again behind it;
+            //   * the window of a task (its column of L_hw / L_hb) is written by ONE thread, in front of the publish of staged[group]:
+            //     the prologue (waves 0 and 1, or r7_fold_into — the R7 instance's threads write only their own task's column), or the
+            //     helper's stage(), every call of which lies in front of its `lds_publish32(staged + g, 1u)`. Behind the publish that
+            //     helper's cursor loop writes L_cur[j] alone (and so does the R7 waves'), the run path's scratch is the group's PICK slots
+            //     (pk_node / pk_idx / pk_aux), the apply reads pk_* and writes global memory, and the fused compact body starts behind
+            //     two barriers that follow the matching. Wave 0 reads a column only behind its acquire of staged[group].
+            // A lane that does not `go` at a stop ignores its pair, as it ignored what it loaded there.
+            u32 ah[R6_SEAT] = {}, ab[R6_SEAT] = {};
+            auto ahead = [&]() {
+                WV_UNROLL
+                for (int q = 0; q < R6_SEAT; ++q) {
+                    const u32 c = min(cur + (u32)q, win - 1u);
+                    R6_REACH(R6R_CLAMPED, have && cur + (u32)q > win - 1u && cur < nent);
+                    ah[q] = L_hw[c * a.block + li];
+                    ab[q] = L_hb[c * a.block + li];
+                }
+            };
+            if (R6_SEAT_AHEAD) ahead();
+            auto seat = [&](bool want) {   // lanes with `want` fill their free seats from their cursor on
+                bool go = want && bits2 == 0 && cur < nent;
+                if (!wv::ballot(go)) return;
+                // (one step; more only as long as a lane has NO seat — a second optional step costs more than the stops it saves. The
+                // loop is tested at its END, behind the request for the next pair: on the way out nothing waits for that request)
+                for ([[maybe_unused]] u32 step = 0;; ++step) {
                     ++seat_steps;
+                    R6_REACH(R6R_SECOND_STEP, step >= 1 && lane == 0);
+                    R6_REACH(R6R_AT_NENT, want && have && cur >= nent);
                     u32 h[R6_SEAT], b[R6_SEAT], t[R6_SEAT];
+                    if (!R6_SEAT_AHEAD) ahead();
                     WV_UNROLL
                     for (int q = 0; q < R6_SEAT; ++q) {
-                        const u32 c = min(cur + (u32)q, win - 1u);
-                        h[q] = L_hw[c * a.block + li];
-                        b[q] = L_hb[c * a.block + li];
+                        h[q] = ah[q];
+                        b[q] = ab[q];
                     }
                     WV_UNROLL
                     for (int q = 0; q < R6_SEAT; ++q) t[q] = tk32[h[q]];
@@ -938,6 +980,12 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                         adv += open ? 1u : 0u;
                     }
                     cur += adv;
+                    if (R6_SEAT_AHEAD) {   // (every lane: one that did not move asks for the same pair again)
+                        R6_SCHED_FENCE();  // (behind the selects, which read the old pair: requested above them the new pair needs registers of its own and a copy — a wait — at the loop's end)
+                        ahead();
+                    }
+                    go = want && bits2 == 0 && cur < nent;
+                    if (!wv::ballot(go && bits == 0)) break;
                 }
             };
             // ---- A group that is ONE RUN of identical tasks (service-major batches: a service's tasks follow each other) needs no walk.
@@ -1011,7 +1059,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             }
             const u64 tgb = prof ? wv::clock64() : 0;
             if (prof && g0 >= 128u) late_runs += fdone;   // (reported with the timers)
-            if (fdone < glim) seat(plain && lane >= fdone, 1u);   // (a second optional step costs more than the stops it saves)
+            if (fdone < glim) seat(plain && lane >= fdone);   // (a second optional step costs more than the stops it saves)
             const u64 tgc = prof ? wv::clock64() : 0;
             if (prof) { cy_g0 += tga - tg0; cy_g1 += tgb - tga; cy_g2 += tgc - tgb; cy_h0 += th0 - tga; cy_h1 += th1 - th0; cy_h2 += tgb - th1; }
             const u64 lanes = glim == 64 ? ~0ull : (1ull << glim) - 1ull;
@@ -1031,6 +1079,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             }
             u32 m_pick = R6_NONE;
             if (g0 == 0 && (m_exc & 1ull)) {   // the block's first task, from its exception list; the block ends behind it
+                R6_REACH(R6R_FIRST_EXC, lane == 0);
                 if (lane == 0) {
                     pk_node[0] = (u32)exc0_lo + 64u * VW;   // (an address, like the matcher's picks)
                     pk_idx[0] = nc;
@@ -1053,10 +1102,32 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             u32 flushed = fdone;   // picks of lanes < flushed are in the TK row
             const u64 tg1 = prof ? wv::clock64() : 0;
             if (lane < fdone) { w = fr_w; pickb = fr_b; }   // (the runs' picks are known: the walk starts behind them)
+            u64 tw_out = 0;     // (timers: the end of the group's last walk so far; written and read under `prof` only — a copy of a clock value
+                                // on the production path is a wait for everything this wave has in flight)
+            u32 walks_g = 0;
+            [[maybe_unused]] u32 gstops = 0;   // (R6_REACH only)
+            R6_REACH(R6R_SHORT_GROUP, lane == 0 && glim < 64u && fdone < cut);
+            R6_REACH(R6R_ONE_ENTRY, have && served && win == 1u);
+            R6_REACH(R6R_BEHIND_RUNS, lane == 0 && fdone > 0 && fdone < cut);
+            R6_REACH(R6R_UNCOUNTED, lane == 0 && m_unc != 0);
+            R6_REACH(R6R_MOUNTS, have && (tflags & 2u));
+            R6_REACH(R6R_COMPACT, lane == 0 && CPT && VW != 0);
+            R6_REACH(R6R_R7, lane == 0 && R7);
             if (fdone < cut) for (;;) {
+                const u64 tw_in = prof ? wv::clock64() : 0;
                 const u32 at = wv::match_seq64(bits, w, bits2, w2, pickb, lane, from);
+                if (prof) {   // (tw_in is first used here, behind the walk: no wait for the clock in front of it)
+                    const u64 tw = wv::clock64();
+                    cy_s0 += tw - tw_in;
+                    if (walks_g) cy_s1 += tw_in - tw_out;
+                    tw_out = tw;
+                    ++walks;
+                    ++walks_g;
+                }
                 if (at >= cut) break;
                 ++reseats;
+                R6_REACH(R6R_THREE_STOPS, lane == 0 && ++gstops == 3u);
+                R6_REACH(R6R_IDLE_LANES, lane > at && served && !(bits2 == 0 && cur < nent));
                 // task `at` ran out of both its half-words — and so, usually, did others that sat on them: this group's picks so far go to
                 // the TK row (a pick = the lowest bit the lane had at its turn, in the half-word it still sits on), and every lane still
                 // to be served fills its free seats from its cursor on
@@ -1064,7 +1135,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 flushed = at;
                 wv::lockstep();   // one wave's LDS operations execute in order: the reads below see the atomics above
                 {
-                    seat(served && lane >= at, 1u);
+                    seat(served && lane >= at);
                     if (wv::readlane(bits, at) == 0) {   // every listed node is taken: propose again against the new state
                         if (prof && lane == at) {   // (off the production path: the list's length from the record itself)
                             const u32 ncd = R7 ? H_meta[li] & 0xFFu : a.prop[li].n_cand;
@@ -1074,6 +1145,11 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                         }
                         cut = at;
                         why = wv::readlane(left_out, at) ? 4 : 1;   // (4: its window ran out, its list had more)
+                        if (prof) {   // (a stop no walk follows)
+                            const u64 tw = wv::clock64();
+                            cy_s1 += tw - tw_out;
+                            tw_out = tw;
+                        }
                         break;
                     }
                 }
@@ -1102,6 +1178,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             else why = 0;
             wv::wave_sync();
             if (lane == 0) wv::lds_publish32(sh + 3, acc);   // the picks of tasks < acc are in the pk arrays: their wave applies them now
+            if (prof) cy_s2 += wv::clock64() - (walks_g ? tw_out : tg1);
         }
         if (lane == 0) {
             sh[0] = acc;
@@ -1132,7 +1209,12 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 a.blk->cyc_h[1] += (u32)(cy_h1 >> 6);
                 a.blk->cyc_h[2] += (u32)(cy_h2 >> 6);
                 a.blk->dbg_late_runs += late_runs;
+                a.blk->cyc_s[0] += (u32)(cy_s0 >> 6);
+                a.blk->cyc_s[1] += (u32)(cy_s1 >> 6);
+                a.blk->cyc_s[2] += (u32)(cy_s2 >> 6);
+                a.blk->dbg_walks += walks;
             }
+            R6_REACH(R6R_ROUND, r6_reach_round(a.blk, pos, acc, why, seat_steps, reseats, pk_node, pk_idx, pk_aux));   // (tests/emu: a round's outcome, for the comparison of two builds)
         }
     }
     const u64 t2 = prof ? wv::clock64() : 0;
