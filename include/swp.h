@@ -379,11 +379,34 @@ void swp_batch_free(swp_engine*, swp_batch*);
  *     Explain rows or the attachments are copied back) is returned with the batch decided, delivered and in the mirror, as it is when
  *     swp_batch_fetch fails behind swp_batch_run_streamed.
  *   - A shard set and the shard / rank protocols refuse these entries with SWP_EUNSUPPORTED (nothing is written); task groups
- *     have no streamed form. */
+ *     are streamed by swp_schedule_groups_streamed below. */
 typedef int (*swp_prefix_sink)(void* ctx, uint32_t first, uint32_t count, const int32_t* nodes);
 int swp_batch_run_streamed(swp_engine*, swp_batch*, int32_t* out_node, swp_prefix_sink sink, void* ctx, uint32_t min_tasks);
 int swp_schedule_batch_streamed(swp_engine*, const swp_task_desc* tasks, uint32_t n_tasks, int32_t* out_node, uint32_t* out_fail_hist,
                                 swp_prefix_sink sink, void* ctx, uint32_t min_tasks);
+
+/* The streamed tick of task groups: swp_schedule_groups (with out_att: swp_schedule_groups_volumes; out_att and out_fail_hist may be
+ * NULL) whose placements reach `sink` while later groups are still decided. A tick is ONE launch that decides group after group, so
+ * the kernel itself publishes: behind a group, once SWP_STREAM_GROUP_TASKS tasks or more (environment, read per call, default 1024;
+ * a tick of more than 2048 groups: at least Σ sizes / 2048) were decided since the last publish, and behind the last group.
+ *   - The sink runs on the calling thread, inside the call.
+ *   - The ranges [first, first + count) are in task units, contiguous, ascending and do not overlap; every range ends at a group
+ *     boundary; on SWP_OK they cover [0, Σ sizes) exactly once.
+ *   - nodes[i] is final: what swp_schedule_groups writes to out_node[first + i], -1 (left over) included. `nodes` points into out_node.
+ *   - Every range but the last holds at least min_tasks tasks. With min_tasks = 0 every publish is one call: the sequence of calls is
+ *     a function of `sizes` and SWP_STREAM_GROUP_TASKS, never of host timing.
+ *   - When the sink sees a range, the node mirror (swp_node_get, swp_node_get_svc_count, swp_node_get_generic) already holds it.
+ *   - out_fail_hist and out_att are complete when the call returns, not earlier (a group's Explain counters are taken one group late).
+ *   - n_groups == 0: no call. An empty nodeSet: ONE call with every task at -1.
+ *   - A non-zero return from the sink ends the tick: SWP_ECANCELLED, whether or not the kernel saw the request before its last group;
+ *     swp_last_error names the range and the group the kernel stopped after.
+ *   - On ANY return but SWP_OK every range already delivered is void: node rows, per-service counts, generic counts and the volumes'
+ *     usage are as before the call (mirror and device), out_node, out_fail_hist and out_att are unspecified.
+ *   - A shard set refuses the entry with SWP_EUNSUPPORTED: nothing is written, the sink is not called.
+ *   - Argument checks and refusals are swp_schedule_groups' (an empty group, more generic kinds than the engine takes, ...). */
+int swp_schedule_groups_streamed(swp_engine*, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups,
+                                 int32_t* out_node, uint32_t* out_fail_hist, uint32_t* out_att,
+                                 swp_prefix_sink sink, void* ctx, uint32_t min_tasks);
 
 /* Device-side snapshot / restore of all mutable node state (cpu, mem, total, per-service counts,
  * host ports) so that a benchmark can replay the same batch from the same state. */

@@ -995,6 +995,59 @@ func (sch *Scheduler) scheduleGroupsSWP(ctx context.Context, groups []map[string
 	}
 }
 
+// scheduleGroupsStreamedSWP: the grouped tick through swp_schedule_groups_streamed, for a call without cluster mounts (descs, sizes,
+// order, all as scheduleGroupsSWP builds them): the tick is ONE launch that decides group after group, and the kernel itself hands out
+// what is decided — a range always ends at a group boundary and holds at least min_tasks tasks (200: a store transaction's worth), so
+// applySchedulingDecisions (scheduler.go:490-643) can start on the first groups while the later ones are still decided. The trampoline
+// is scheduleOneOffsStreamedSWP's (swpPrefixSink), and so is the rule: nothing delivered is valid unless the call returns SWP_OK — the
+// sink stages decisions (assign) and commits nothing; on any other code the engine's side is already as before the call and the staged
+// decisions go. A group's Explain counters (and a call's attachments) are complete only when the call returns: tasks without a node are
+// handled behind it.
+func (sch *Scheduler) scheduleGroupsStreamedSWP(ctx context.Context, descs []C.swp_task_desc, sizes []C.uint32_t, order [][]*api.Task, all []*api.Task,
+	decisions map[string]schedulingDecision) bool {
+	out := make([]C.int32_t, len(all))
+	hist := make([]C.uint32_t, len(descs)*C.SWP_NFILTERS)
+	staged := 0 // tasks [0, staged) of `all` have their decision
+	sink := func(first int, nodes []C.int32_t) C.int {
+		if ctx.Err() != nil {
+			return 1 // SWP_ECANCELLED: the kernel ends at the next group it publishes, the engine rolls the ranges back
+		}
+		for i, n := range nodes {
+			if n >= 0 {
+				sch.assign(ctx, all[first+i], sch.swp.idxNode[n], nil, decisions)
+			}
+		}
+		staged = first + len(nodes)
+		return 0
+	}
+	h := cgo.NewHandle(sink)
+	defer h.Delete()
+	rc := C.swp_schedule_groups_streamed(sch.swp.e, &descs[0], &sizes[0], C.uint32_t(len(descs)), &out[0], &hist[0], nil,
+		C.swp_prefix_sink(C.swpPrefixSink), unsafe.Pointer(uintptr(h)), 200)
+	if rc != C.SWP_OK {
+		for _, t := range all[:staged] { // every delivered range is void (not through rollbackSWP: the engine has taken them out itself)
+			if d, ok := decisions[t.ID]; ok {
+				if ni, err := sch.nodeSet.nodeInfo(d.new.NodeID); err == nil {
+					delete(ni.Tasks, d.new.ID)
+					sch.nodeSet.updateNode(ni)
+				}
+				delete(decisions, t.ID)
+			}
+		}
+		return false // the caller falls back to scheduleGroupsSWP or the Go path
+	}
+	i := 0
+	for g, ts := range order {
+		for _, t := range ts {
+			if out[i] < 0 {
+				sch.noSuitableNodeWith(ctx, t, explainFromHist(hist[g*C.SWP_NFILTERS:(g+1)*C.SWP_NFILTERS]), decisions)
+			}
+			i++
+		}
+	}
+	return true
+}
+
 // rollbackSWP: the failed half of applySchedulingDecisions (scheduler.go:472-487): the reference already restores allTasks,
 // calls nodeInfo.removeTask(decision.new) and enqueues decision.old; the engine side of removeTask is one swp_commit(remove).
 func (sch *Scheduler) rollbackSWP(failed []schedulingDecision) {

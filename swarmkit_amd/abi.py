@@ -111,7 +111,7 @@ EXPORTS = [
     "swp_create", "swp_destroy", "swp_reset", "swp_intern", "swp_intern_lookup", "swp_node_upsert", "swp_node_update_dynamic",
     "swp_node_remove", "swp_node_get", "swp_node_set_svc_count", "swp_node_get_svc_count", "swp_node_set_failures", "swp_node_port",
     "swp_constraint_set", "swp_platform_set", "swp_plugin_set", "swp_port_set", "swp_spread_set", "swp_schedule_groups", "swp_schedule_batch", "swp_batch_prepare",
-    "swp_batch_run", "swp_batch_run_streamed", "swp_schedule_batch_streamed", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_enforce_generic", "swp_node_matches",
+    "swp_batch_run", "swp_batch_run_streamed", "swp_schedule_batch_streamed", "swp_schedule_groups_streamed", "swp_batch_fetch", "swp_batch_results", "swp_batch_free", "swp_state_save", "swp_state_restore", "swp_commit", "swp_check_node", "swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce", "swp_enforce_generic", "swp_node_matches",
     "swp_stats", "swp_strerror", "swp_last_error", "swp_abi_check", "swp_node_update_dynamic_many", "swp_node_get_many", "swp_shardset_create",
     "swp_shard_begin", "swp_shard_propose", "swp_shard_merge", "swp_shard_commit", "swp_shard_end", "swp_shard_run", "swp_rccl_available", "swp_rccl_unique_id", "swp_rccl_init", "swp_rccl_finalize", "swp_shard_run_rank", "swp_shard_verdict",
     # include/swp_sched.h — the host layer above the engine
@@ -121,7 +121,7 @@ EXPORTS = [
     "swp_constraint_parse", "swp_key_equal_fold", "swp_explain", "swp_parse_ip",
 ]
 # exports a library built against this header may lack (the host layer's CPU test double): the host layer declares them weak
-OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce_generic", "swp_batch_run_streamed", "swp_schedule_batch_streamed"}
+OPTIONAL = {"swp_fit_pairs", "swp_fit_pairs_volumes", "swp_enforce_generic", "swp_batch_run_streamed", "swp_schedule_batch_streamed", "swp_schedule_groups_streamed"}
 # swp_prefix_sink: int (*)(void* ctx, uint32_t first, uint32_t count, const int32_t* nodes) — called on the calling thread, inside the call
 PREFIX_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32))
 MAX_MOUNTS = 8              # SWP_MAX_MOUNTS
@@ -201,6 +201,7 @@ def load_library(path=None):
         "swp_batch_run": ([vp, vp], C.c_int),
         "swp_batch_run_streamed": ([vp, vp, vp, PREFIX_SINK, vp, u32], C.c_int),
         "swp_schedule_batch_streamed": ([vp, vp, u32, vp, vp, PREFIX_SINK, vp, u32], C.c_int),
+        "swp_schedule_groups_streamed": ([vp, vp, vp, u32, vp, vp, vp, PREFIX_SINK, vp, u32], C.c_int),
         "swp_batch_fetch": ([vp, vp, vp, vp], C.c_int),
         "swp_batch_results": ([vp, vp, vp, vp], C.c_int),
         "swp_batch_free": ([vp, vp], None),
@@ -577,6 +578,27 @@ class Engine:
         hist = np.zeros((len(groups), NFILTERS), dtype=np.uint32)
         self._ck(self.L.swp_schedule_groups(self.h, groups.ctypes.data, sizes.ctypes.data, len(groups), out.ctypes.data, hist.ctypes.data))
         return out, hist
+
+    def schedule_groups_streamed(self, groups, sizes, sink, min_tasks=0, want_hist=True, want_att=False):
+        """swp_schedule_groups_streamed: schedule_groups whose placements reach `sink` while later groups are decided. sink(first, nodes)
+        is called on this thread for contiguous, ascending ranges in task units that end at group boundaries and cover the tick exactly
+        once; nodes is an int32 view (valid during the call) of the final placements, and the node mirror already holds them. Every
+        range but the last has at least min_tasks tasks. A true return value (or an exception, raised again here) ends the tick:
+        SwpError(SWP_ECANCELLED), nothing applied. Returns (out_node int32[sum sizes], hist uint32[n_groups, 8] or None), and with
+        want_att a third array uint32[sum sizes, MAX_MOUNTS] as schedule_groups_volumes gives it."""
+        groups = np.ascontiguousarray(groups, dtype=TASK_DTYPE)
+        sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
+        total = int(sizes.sum())
+        out = np.empty(total, dtype=np.int32)
+        hist = np.zeros((len(groups), NFILTERS), dtype=np.uint32) if want_hist else None
+        att = np.full((total, MAX_MOUNTS), NO_VOLUME, dtype=np.uint32) if want_att else None
+        cb, raised = _prefix_sink(sink, out)
+        rc = self.L.swp_schedule_groups_streamed(self.h, groups.ctypes.data, sizes.ctypes.data, len(groups), out.ctypes.data, hist.ctypes.data if want_hist else None,
+                                                 att.ctypes.data if want_att else None, cb, None, int(min_tasks))
+        if raised:
+            raise raised[0]
+        self._ck(rc)
+        return (out, hist, att) if want_att else (out, hist)
 
     def enforce(self, nodes, tasks, out=None):
         """constraintenforcer.rejectNoncompliantTasks over many nodes. nodes: ENF_NODE_DTYPE, tasks: ENF_TASK_DTYPE

@@ -2335,8 +2335,25 @@ void host_apply_bulk(swp_engine* e, const std::vector<BulkItem>& it, bool add, B
 // ---- the streamed run (include/swp.h swp_batch_run_streamed) ----
 // What batch_run_impl's streamed variant carries: the marks' arithmetic (swp_rounds.hpp StreamMarks), k_publish's arguments, and the
 // books of what went into the node mirror so far — every failure exit takes exactly that out again.
+// task of a streamed run -> its descriptor: the batch's own mapping, or — a tick of task groups — through the groups' bounds (a cursor:
+// the deliveries walk the tasks forwards, the rollback backwards)
+struct StreamDesc {
+    const swp_batch* b = nullptr;
+    const swp_task_desc* groups = nullptr;
+    const uint32_t* ends = nullptr;   // [n_groups] first task behind each group
+    mutable uint32_t g = 0;
+    const swp_task_desc& operator()(uint32_t i) const {
+        if (!groups) return b->desc(i);
+        while (i >= ends[g]) ++g;
+        while (g && i < ends[g - 1]) --g;
+        return groups[g];
+    }
+};
 struct StreamRun {
     swp_batch* b;
+    StreamDesc desc;
+    uint32_t* h_cancel = nullptr;   // a tick of task groups: the word its one long launch looks at (set when the sink cancels)
+    bool vols = false;              // ... and whether its groups reserve volumes
     int32_t* out_node;
     swp_prefix_sink sink;
     void* ctx;
@@ -2349,18 +2366,22 @@ struct StreamRun {
     std::vector<std::pair<uint32_t, uint32_t>> folded;   // (first, count) of the ranges in the mirror, in delivery order
     std::unordered_map<uint32_t, std::vector<std::pair<uint32_t, int64_t>>> gen_before;   // generic counts of the nodes a fold changed them on, as they were
     uint64_t placed = 0;
-    StreamRun(swp_batch* b_, int32_t* out, swp_prefix_sink s, void* c, uint32_t min_tasks) : b(b_), out_node(out), sink(s), ctx(c), marks(b_->T, min_tasks), every(stream_every()) {}
+    StreamRun(swp_batch* b_, int32_t* out, swp_prefix_sink s, void* c, uint32_t min_tasks) : b(b_), out_node(out), sink(s), ctx(c), marks(b_->T, min_tasks), every(stream_every()) { desc.b = b_; }
+    // a tick of task groups: `b_` is the call's own batch (one descriptor per group), the tasks are the groups' (swp_schedule_groups_streamed)
+    StreamRun(swp_batch* b_, const swp_task_desc* groups, const uint32_t* ends, uint32_t n_tasks, int32_t* out, swp_prefix_sink s, void* c, uint32_t min_tasks)
+        : b(b_), out_node(out), sink(s), ctx(c), marks(n_tasks, min_tasks), every(0) { desc.groups = groups; desc.ends = ends; }
     ~StreamRun() { if (ev) (void)hipEventDestroy(ev); }
     const uint32_t* h_count() const { return pa.h_count; }
 };
 constexpr size_t PUB_HDR = 64;   // the mark counter's line in front of the ring
+constexpr size_t PUB_CANCEL = 32;   // ... and in it the cancel word of a streamed tick of task groups
 
 uint32_t stream_rounds(const StreamRun* sx) { return sx->every; }
 
 // the pinned block and the device words, as a run starts: no mark, nothing published, every placement the sentinel
 int stream_begin(swp_engine* e, StreamRun* sx) {
     swp_batch* b = sx->b;
-    const uint32_t T = b->T;
+    const uint32_t T = sx->marks.T;
     // k_publish's stores must reach host DRAM while the kernel runs and be seen by a host that polls: FINE-GRAINED (host-coherent) pinned
     // memory. The pinned pool allocates with hipHostMallocDefault, i.e. without flags, and that is coherent memory in this runtime
     // (hipHostMallocNonCoherent, or flags with HIP_HOST_COHERENT=0, would not be); the flags of the block are checked here, so a pool
@@ -2391,7 +2412,6 @@ int stream_begin(swp_engine* e, StreamRun* sx) {
 
 // one range: checked, into the mirror, into the caller's array, to the sink
 int stream_deliver(swp_engine* e, StreamRun* sx, uint32_t first, uint32_t count) {
-    swp_batch* b = sx->b;
     const int32_t* src = sx->pa.h_pub + first;
     for (uint32_t i = 0; i < count; ++i) {   // nothing of a range is folded before all of it is known to be good
         const int32_t n = src[i];
@@ -2402,7 +2422,7 @@ int stream_deliver(swp_engine* e, StreamRun* sx, uint32_t first, uint32_t count)
     for (uint32_t i = 0; i < count; ++i) {
         const int32_t n = src[i];
         if (n < 0) continue;
-        const swp_task_desc& d = b->desc(first + i);
+        const swp_task_desc& d = sx->desc(first + i);
         if (!d.port_set && !d.generic_set && !(d.flags & 0x2u)) sx->bulk.push_back(BulkItem{(uint32_t)n, d.service, d.cpu, d.mem});
         else {
             if (d.generic_set && !sx->gen_before.count((uint32_t)n)) sx->gen_before.emplace((uint32_t)n, e->nodes[n].gen);
@@ -2413,7 +2433,10 @@ int stream_deliver(swp_engine* e, StreamRun* sx, uint32_t first, uint32_t count)
     host_apply_bulk(e, sx->bulk, true, sx->scr);
     sx->folded.emplace_back(first, count);
     std::memcpy(sx->out_node + first, src, (size_t)count * 4);
-    if (sx->sink && sx->sink(sx->ctx, first, count, sx->out_node + first) != 0) return e->fail(SWP_ECANCELLED, "the sink cancelled the batch at the range [%u, %u)", first, first + count);
+    if (sx->sink && sx->sink(sx->ctx, first, count, sx->out_node + first) != 0) {
+        if (sx->h_cancel) __atomic_store_n(sx->h_cancel, 1u, __ATOMIC_RELEASE);   // (the tick's launch ends at the next publish it executes)
+        return e->fail(SWP_ECANCELLED, "the sink cancelled the batch at the range [%u, %u)", first, first + count);
+    }
     return SWP_OK;
 }
 
@@ -2476,7 +2499,7 @@ void stream_rollback(swp_engine* e, StreamRun* sx) {
         for (uint32_t i = count; i-- > 0;) {
             const int32_t n = sx->pa.h_pub[first + i];   // (the engine's own copy: the caller may have written to its array)
             if (n < 0) continue;
-            const swp_task_desc& d = b->desc(first + i);
+            const swp_task_desc& d = sx->desc(first + i);
             if (!d.port_set && !d.generic_set && !(d.flags & 0x2u)) sx->bulk.push_back(BulkItem{(uint32_t)n, d.service, d.cpu, d.mem});
             else host_apply_placement(e, (uint32_t)n, d.service, d.cpu, d.mem, d.port_set, !(d.flags & 0x2u), false);
         }
@@ -2486,7 +2509,7 @@ void stream_rollback(swp_engine* e, StreamRun* sx) {
     sx->folded.clear();
     sx->gen_before.clear();
     e->dev_dynamic_dirty = true;
-    if (!b->csi_set.empty()) e->vol_dyn_dirty = true;   // (the device's usage numbers moved with the rounds, the host's did not)
+    if (!b->csi_set.empty() || sx->vols) e->vol_dyn_dirty = true;   // (the device's usage numbers moved with the rounds, the host's did not)
     // ... and at once, not at the next swp_batch_prepare: the caller may run this very batch again (a run itself uploads no node rows).
     // Should the upload fail, the flag stays and the next preparation tries again.
     (void)flush_nodes(e);
@@ -3140,20 +3163,78 @@ int swp_node_get_generic(swp_engine* e, uint32_t node, uint32_t kind, int64_t* c
     return SWP_OK;
 }
 
-static int groups_apply_to_host(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, uint64_t total, const int32_t* out_node);
+static int groups_apply_to_host(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, uint64_t total, const int32_t* out_node, const uint64_t* folded_placed = nullptr);
 
-static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, int32_t* out_node, uint32_t* out_fail_hist, uint32_t* out_att);
+struct GroupSink {   // swp_schedule_groups_streamed: where the ranges go
+    swp_prefix_sink sink;
+    void* ctx;
+    uint32_t min_tasks;
+};
+static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, int32_t* out_node, uint32_t* out_fail_hist, uint32_t* out_att,
+                                const GroupSink* gs = nullptr);
 int swp_schedule_groups(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, int32_t* out_node,
                         uint32_t* out_fail_hist) {
     return schedule_groups_impl(e, groups, sizes, n_groups, out_node, out_fail_hist, nullptr);
+}
+int swp_schedule_groups_streamed(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, int32_t* out_node, uint32_t* out_fail_hist,
+                                 uint32_t* out_att, swp_prefix_sink sink, void* ctx, uint32_t min_tasks) {
+    if (!e) return SWP_EINVAL;
+    if (e->set) return e->fail(SWP_EUNSUPPORTED, "a shard set has no streamed tick of task groups");
+    const GroupSink gs{sink, ctx, min_tasks};
+    return schedule_groups_impl(e, groups, sizes, n_groups, out_node, out_fail_hist, out_att, &gs);
 }
 int swp_schedule_groups_volumes(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, int32_t* out_node,
                                 uint32_t* out_fail_hist, uint32_t* out_att) {
     if (!out_att && n_groups) return SWP_EINVAL;
     return schedule_groups_impl(e, groups, sizes, n_groups, out_node, out_fail_hist, out_att);
 }
+// What the streamed tick does from the launch on (below): the launch of k_groups2s, the result copies behind it, the marks serviced
+// while it runs. `res`: pinned, [Ctl][stop word, pad][hist][attachments][volume usage] as far as the call has them.
+struct GroupsStreamCopies {
+    const void* d_hist; size_t hist_bytes;
+    const void* d_att; size_t att_bytes;
+    const void* d_vdyn; size_t vdyn_bytes;
+};
+static int groups_stream_run(swp_engine* e, StreamRun* sx, const Groups2Args& ga, const uint32_t* sizes, uint32_t n_groups, char* res, const GroupsStreamCopies& cp, bool timed) {
+    hipStream_t st = e->stream;
+    swp_batch* b = sx->b;
+    char* base = static_cast<char*>(b->h_pubblk.p);
+    G2Pub pb{};
+    pb.h_pub = sx->pa.h_pub; pb.h_ring = sx->pa.h_ring; pb.h_count = sx->pa.h_count;
+    pb.h_cancel = sx->h_cancel = reinterpret_cast<uint32_t*>(base + PUB_CANCEL);
+    pb.d_stop = b->d_pubstate.as<uint32_t>();
+    pb.ring = StreamMarks::RING;
+    pb.step = group_pub_step(sx->marks.T, n_groups, stream_group_tasks());
+    sx->marks.enqueued = group_marks(sizes, n_groups, pb.step, [](uint32_t, uint32_t) {});   // the kernel appends exactly these, whatever the host does meanwhile
+    if (sx->marks.enqueued > StreamMarks::RING / 2) return e->fail(SWP_ERANGE, "%u marks for a ring of %u", sx->marks.enqueued, StreamMarks::RING);
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (timed) { (void)hipEventCreate(&t0); (void)hipEventCreate(&t1); (void)hipEventRecord(t0, st); }   // (SWP_DBG=16: the two launches, as the plain call times its own)
+    hipError_t r = launch_groups2_streamed(ga, pb, st, e->device);
+    if (r == hipSuccess && t1) r = hipEventRecord(t1, st);
+    // the results that are complete only when the tick is: behind the launch, into pinned memory (a copy into the caller's pageable
+    // arrays would hold this thread until the kernel is through — the thread that has marks to service)
+    size_t off = 0;
+    if (r == hipSuccess) r = hipMemcpyAsync(res, b->d_ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, st);
+    off += sizeof(Ctl);
+    if (r == hipSuccess) r = hipMemcpyAsync(res + off, b->d_pubstate.p, 8, hipMemcpyDeviceToHost, st);
+    off += 8;
+    if (r == hipSuccess && cp.hist_bytes) r = hipMemcpyAsync(res + off, cp.d_hist, cp.hist_bytes, hipMemcpyDeviceToHost, st);
+    off += cp.hist_bytes;
+    if (r == hipSuccess && cp.att_bytes) r = hipMemcpyAsync(res + off, cp.d_att, cp.att_bytes, hipMemcpyDeviceToHost, st);
+    off += cp.att_bytes;
+    if (r == hipSuccess && cp.vdyn_bytes) r = hipMemcpyAsync(res + off, cp.d_vdyn, cp.vdyn_bytes, hipMemcpyDeviceToHost, st);
+    int rc = r == hipSuccess ? SWP_OK : e->fail(SWP_EHIP, "the streamed tick's launch: %s", hipGetErrorString(r));
+    if (rc == SWP_OK) rc = stream_wait(e, sx, true);   // the event behind all of it; marks are serviced while it is not through, the rest then
+    if (t0 && t1) {
+        float ms = 0;
+        if (rc == SWP_OK && hipEventElapsedTime(&ms, t0, t1) == hipSuccess) fprintf(stderr, "[swp] k_groups2s %.3f ms for %u groups, %u marks at a step of %u tasks\n", ms, n_groups, sx->marks.enqueued, pb.step);
+        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    }
+    return rc;
+}
+
 static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, int32_t* out_node,
-                                uint32_t* out_fail_hist, uint32_t* out_att) {
+                                uint32_t* out_fail_hist, uint32_t* out_att, const GroupSink* gs) {
     if (!e || (!groups && n_groups) || (!sizes && n_groups)) return SWP_EINVAL;
     if (n_groups == 0) return SWP_OK;
     if (e->set) return ss::schedule_groups(e, groups, sizes, n_groups, out_node, out_fail_hist, out_att);
@@ -3170,6 +3251,8 @@ static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, cons
     const uint32_t N = e->n_nodes, Wn = n_words_of(N);
     if (N == 0) {   // empty nodeSet: every task is left over, empty explanation
         for (uint64_t i = 0; i < total; ++i) out_node[i] = -1;
+        if (gs && out_att) std::fill(out_att, out_att + (size_t)total * SWP_MAX_MOUNTS, SWP_NO_VOLUME);
+        if (gs && gs->sink && gs->sink(gs->ctx, 0, (uint32_t)total, out_node) != 0) return e->fail(SWP_ECANCELLED, "the sink cancelled the tick at the range [0, %u)", (uint32_t)total);
         return SWP_OK;
     }
     HostSpan sp("groups: build_batch + upload");
@@ -3357,6 +3440,66 @@ static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, cons
         ga.att = d_gatt.as<uint32_t>();
     }
     sp.next("groups: k_groups2 + download");
+    if (gs) {
+        // The streamed tick. Everything up to here is the plain call's; from here on every failure takes the streamed run's one way out
+        // (stream_rollback): the ranges leave the mirror again, generic counts come back, the device rows are uploaded again.
+        if (gev0) { (void)hipEventDestroy(gev0); (void)hipEventDestroy(gev1); }   // (SWP_DBG=16: this path times its kernel itself)
+        std::vector<uint32_t> ends(n_groups);
+        for (uint32_t g = 0; g < n_groups; ++g) ends[g] = recs[g].out_off + sizes[g];
+        StreamRun sx(&b, groups, ends.data(), (uint32_t)total, out_node, gs->sink, gs->ctx, gs->min_tasks);
+        sx.vols = att_rows != 0;
+        const size_t hist_bytes = out_fail_hist ? (size_t)n_groups * 8 * 4 : 0, att_bytes = (size_t)att_rows * SWP_MAX_MOUNTS * 4;
+        const size_t vdyn_bytes = att_rows ? e->volumes.size() * sizeof(swp_volume_usage) : 0;
+        PinBuf h_res;
+        rc = stream_begin(e, &sx);
+        if (rc == SWP_OK) {
+            const hipError_t r = h_res.reserve(sizeof(Ctl) + 8 + hist_bytes + att_bytes + vdyn_bytes);
+            if (r != hipSuccess) rc = e->fail(SWP_EHIP, "pinned memory for the tick's results: %s", hipGetErrorString(r));
+        }
+        char* res = static_cast<char*>(h_res.p);
+        if (rc == SWP_OK) {
+            std::memset(res, 0, sizeof(Ctl) + 8);
+            const GroupsStreamCopies cp{d_hist.p, hist_bytes, d_gatt.p, att_bytes, e->d_vdyn.p, vdyn_bytes};
+            rc = groups_stream_run(e, &sx, ga, sizes, n_groups, res, cp, gdbg);
+        }
+        if (rc != SWP_ECANCELLED && res) {   // (a launch the kernel itself ended leaves marks missing: its own word says why, not the ring)
+            Ctl ctl2;
+            std::memcpy(&ctl2, res, sizeof ctl2);
+            if (ctl2.error == ERR_GROUP_HANG) rc = e->fail(SWP_EHIP, "the group kernel's waves lost each other (a wait exceeded its bound): nothing was applied");
+            else if (ctl2.error == ERR_GROUP_CANCELLED) rc = e->fail(SWP_EHIP, "the group kernel saw a cancel word the host never set");
+            else if (ctl2.error != ERR_NONE) rc = e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
+            else if (rc == SWP_OK && !sx.marks.complete()) rc = e->fail(SWP_EHIP, "published range not visible: the marks end at task %u of %u", sx.marks.top, (uint32_t)total);
+        }
+        if (rc != SWP_OK) {
+            std::string why = e->last_error;   // (the wait below must not replace the reason)
+            stream_rollback(e, &sx);           // waits for the launch and the copies behind it
+            if (rc == SWP_ECANCELLED && res) {
+                uint32_t stop = 0;
+                std::memcpy(&stop, res + sizeof(Ctl), 4);
+                char tail[96];
+                snprintf(tail, sizeof tail, "; the kernel stopped after group %u of %u", stop, n_groups);
+                why += tail;
+            }
+            e->last_error = why;
+            return rc;
+        }
+        size_t roff = sizeof(Ctl) + 8;
+        if (out_fail_hist) std::memcpy(out_fail_hist, res + roff, hist_bytes);
+        roff += hist_bytes;
+        if (out_att) std::fill(out_att, out_att + (size_t)total * SWP_MAX_MOUNTS, SWP_NO_VOLUME);
+        if (att_rows) {
+            const uint32_t* h = reinterpret_cast<const uint32_t*>(res + roff);
+            const swp_volume_usage* dyn = reinterpret_cast<const swp_volume_usage*>(res + roff + att_bytes);
+            for (size_t v = 0; v < e->volumes.size(); ++v)
+                if (e->volumes[v].present) e->volumes[v].use = dyn[v];
+            if (out_att)
+                for (uint32_t g = 0; g < n_groups; ++g)
+                    if (recs[g].mset)
+                        std::memcpy(out_att + (size_t)recs[g].out_off * SWP_MAX_MOUNTS, h + (size_t)recs[g].att_off * SWP_MAX_MOUNTS, (size_t)sizes[g] * SWP_MAX_MOUNTS * 4);
+        }
+        sp.next("groups: placements into the node mirror");
+        return groups_apply_to_host(e, groups, sizes, n_groups, total, out_node, &sx.placed);   // (the deliveries folded them: the stats only)
+    }
     HIPCHECK(e, launch_groups2(ga, st, e->device));
     if (gdbg) {
         (void)hipEventRecord(gev1, st);
@@ -3403,12 +3546,13 @@ static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, cons
 }
 
 // the host mirror follows the device: NodeInfo.addTask for every placement of the call
-static int groups_apply_to_host(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, uint64_t total, const int32_t* out_node) {
-    uint64_t placed = 0;
+// folded_placed: a streamed tick — its deliveries put the placements there already (that many of them): only the stats move
+static int groups_apply_to_host(swp_engine* e, const swp_task_desc* groups, const uint32_t* sizes, uint32_t n_groups, uint64_t total, const int32_t* out_node, const uint64_t* folded_placed) {
+    uint64_t placed = folded_placed ? *folded_placed : 0;
     uint32_t off = 0;
     std::vector<BulkItem> bulk;   // (a group's placements are k tasks of one service: the bulk path's merge per service is one per group)
-    bulk.reserve(total);
-    for (uint32_t g = 0; g < n_groups; ++g) {
+    bulk.reserve(folded_placed ? 0 : total);
+    for (uint32_t g = 0; g < n_groups && !folded_placed; ++g) {
         const swp_task_desc& d = groups[g];
         const int32_t* on = out_node + off;
         const uint32_t k = sizes[g];

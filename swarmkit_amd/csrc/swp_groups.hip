@@ -10,19 +10,36 @@ namespace swpdev { __device__ unsigned long long g2_stat_dev[12]; }
 #define G2_STAT(i, v) do { if (wv::lane() == 0) atomicAdd(&swpdev::g2_stat_dev[i], (unsigned long long)(v)); } while (0)
 #endif
 #define SWP_G2_KERNELS
+#define SWP_G2_STREAM   // the streamed instance k_groups2s next to the plain one
 #include "swp_groups.hpp"
 
 namespace swpdev {
 
-// k_g2_static: a wave per static class; then one workgroup for the whole tick: the machine wave + 15 helper waves (swp_groups.hpp)
-hipError_t launch_groups2(const Groups2Args& a, hipStream_t s, int dev) {
-    hipError_t r = ensure_big_lds(reinterpret_cast<const void*>(&k_groups2), dev);
-    if (r != hipSuccess) return r;
+static unsigned g2_threads() {
     unsigned threads = G2_THREADS;
     if (const char* t = getenv("SWP_G2_THREADS")) {   // experiments only: fewer helper waves (a multiple of 64, at least 128)
         const unsigned v = (unsigned)atoi(t);
         if (v >= 128 && v <= G2_THREADS && v % 64 == 0) threads = v;
     }
+    return threads;
+}
+
+// The streamed instance (swp_schedule_groups_streamed): the same two launches, k_groups2s with the host-visible block behind the tick's
+// arguments.
+hipError_t launch_groups2_streamed(const Groups2Args& a, const G2Pub& pb, hipStream_t s, int dev) {
+    hipError_t r = ensure_big_lds(reinterpret_cast<const void*>(&k_groups2s), dev);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(k_g2_static, dim3(a.n_scls), dim3(64), 0, s, a);
+    if ((r = hipGetLastError()) != hipSuccess) return r;
+    hipLaunchKernelGGL(k_groups2s, dim3(1), dim3(g2_threads()), g2_lds_bytes(), s, a, pb);
+    return hipGetLastError();
+}
+
+// k_g2_static: a wave per static class; then one workgroup for the whole tick: the machine wave + 15 helper waves (swp_groups.hpp)
+hipError_t launch_groups2(const Groups2Args& a, hipStream_t s, int dev) {
+    hipError_t r = ensure_big_lds(reinterpret_cast<const void*>(&k_groups2), dev);
+    if (r != hipSuccess) return r;
+    const unsigned threads = g2_threads();
     // the static class lists first (one wave per class, all over the chip), then the tick
     hipLaunchKernelGGL(k_g2_static, dim3(a.n_scls), dim3(64), 0, s, a);
     if ((r = hipGetLastError()) != hipSuccess) return r;

@@ -46,8 +46,9 @@ namespace swpdev {
 #define G2_NONE 0xFFFFFFFFu
 #define ERR_GROUP_HANG 3         // a wave waited for another one beyond any plausible time (protocol bug): the launch ends instead of hanging
 #define G2_SPIN_LIMIT (1u << 26)
+#define ERR_GROUP_CANCELLED 4    // the streamed instance: the host set the cancel word (the caller's sink returned non-zero); the launch ends at the next group
 
-enum { G2_OP_SCATTER = 1, G2_OP_EVAL = 2, G2_OP_EXPLAIN = 3, G2_OP_UNSCATTER = 4, G2_OP_QUIT = 5 };
+enum { G2_OP_SCATTER = 1, G2_OP_EVAL = 2, G2_OP_EXPLAIN = 3, G2_OP_UNSCATTER = 4, G2_OP_QUIT = 5, G2_OP_PUBLISH = 6 };
 
 // One entry of a group's candidate list (Groups2Args.ccand): a node of the group's static class list with its nodeLess key and spread
 // leaf — all the admission scan reads (one 16-byte load per candidate, 64 candidates per "chunk" instead of the handful a node word holds)
@@ -141,6 +142,21 @@ struct Groups2Args {
     // fill loop re-checks a node — and every placement chooses and reserves its volumes (scheduler.go:857-874)
     VolView vol;
     u32* att;                // [tasks of the groups with mounts][VOL_MAX_MOUNTS]
+};
+
+// What the STREAMED instance (k_groups2s, swp_schedule_groups_streamed) gets on top: while the tick runs, the placements of the groups
+// decided so far go to host-visible memory (fine-grained pinned: device stores land in host DRAM) and their end — a MARK — to a ring
+// the host polls, as k_publish does between the rounds of a batch (swp_publish.hpp). There are no rounds here to put a kernel between:
+// the machine posts G2_OP_PUBLISH behind a group when `step` tasks or more were decided since the last one (and behind the last group;
+// the host knows the rule: swp_rounds.hpp group_marks), helper 0 executes it. The kernel never reads the ring back and never waits
+// for the host: `step` is chosen so that a tick's marks fill at most half of the ring.
+struct G2Pub {
+    int32_t* h_pub;         // host-visible [tasks of the call]
+    u32* h_ring;            // host-visible [ring]: the marks, in order
+    u32* h_count;           // host-visible: marks appended so far
+    const u32* h_cancel;    // host-visible: the host sets it when the tick is to end early
+    u32* d_stop;            // device: groups the machine went through before the launch ended
+    u32 step, ring;
 };
 
 struct G2Frame {   // one invocation of scheduleNTasksOnSubtree (scheduler.go:772-825)
@@ -514,13 +530,52 @@ WV_DEV bool g2_wait_ge(const u32* p, u32 want, G2Mail* mb) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // helpers: waves 1 .. nh
 // ---------------------------------------------------------------------------------------------------------------------------
-WV_DEV void g2_helper(const Groups2Args& a, G2Mail* mb, u32 hid, u32 nh) {
+#ifdef SWP_G2_STREAM
+// G2_OP_PUBLISH on helper 0: out_node[from, end of group gi) to the host, then the mark, then the counter — k_publish's order: plain
+// vector stores, a system-scope release fence behind them (one wave: the fence waits for every lane's stores), the mark (relaxed) and
+// the counter (release) from lane 0. The machine stored and waited for (wait_vm) the group's placements before it posted the command.
+// The cancel word is looked at here and nowhere else: an error word the machine reads at every group's start ends the launch.
+WV_DEV void g2_publish(const Groups2Args& a, const G2Pub& pb, u32 gi, u32& from, u32& nmark) {
+    const u32 lane = wv::lane();
+    const GroupRec2* Gm = a.g + gi;
+    const u32 upto = Gm->out_off + Gm->k;
+    for (u32 i = from + lane; i < upto; i += 64u) pb.h_pub[i] = a.out_node[i];
+    wv::sys_fence();
+    wv::lockstep();   // (the CPU fibers: every lane has copied its share before lane 0 says so)
+    if (lane == 0) {
+        wv::sys_store32(&pb.h_ring[nmark % pb.ring], upto);
+        wv::sys_store_release32(pb.h_count, nmark + 1u);
+        if (wv::sys_load32(pb.h_cancel) != 0u) a.ctl->error = ERR_GROUP_CANCELLED;
+    }
+    from = upto;
+    nmark += 1u;
+}
+#endif
+#ifndef G2_HELPER_AT
+#define G2_HELPER_AT(hid, my) ((void)0)   // (the CPU-fiber build of the streamed instance: how far each helper has read the ring)
+#endif
+// PUB: the streamed instance (G2Pub) — the plain one carries none of it
+template <bool PUB>
+WV_DEV void g2_helper(const Groups2Args& a, const G2Pub& pb, G2Mail* mb, u32 hid, u32 nh) {
     const u32 lane = wv::lane(), N = a.n_nodes, Wn = a.n_words;
+    u32 pub_from = 0, pub_marks = 0;   // helper 0 of the streamed instance: tasks published, marks appended
+    (void)pub_from; (void)pub_marks; (void)pb;
     for (u32 my = 0;; ++my) {
         if (!g2_wait_ge(&mb->posted, my + 1, mb)) return;
         if (!g2_wait_ge(&mb->done, my * nh, mb)) return;   // every helper is through the command before: its writes are this one's inputs
         const u32 op = mb->op[my % G2_RING], gi = mb->grp[my % G2_RING];
+        G2_HELPER_AT(hid, my);
         if (op == G2_OP_QUIT) return;
+#ifdef SWP_G2_STREAM
+        if constexpr (PUB) {
+            if (op == G2_OP_PUBLISH) {   // helper 0 publishes, the others only count the command done
+                if (hid == 0) g2_publish(a, pb, gi, pub_from, pub_marks);
+                wv::lockstep();
+                if (lane == 0) wv::lds_add_release32(&mb->done, 1u);
+                continue;
+            }
+        }
+#endif
         const GroupRec2* Gm = a.g + gi;
         const GroupRec2 G = *Gm;
         const u32 b = gi & 1u;
@@ -729,7 +784,17 @@ WV_DEV void g2_flat_flush(const G2Arena& A, G2Flat& F, u32 k, const u32* cand, c
 struct G2Post {   // wave 0's view of the ring
     u32 n;        // commands posted
 };
+// The ring has G2_RING = 16 entries and nobody checks for room: at most 8 commands are ever outstanding. At a group's start the machine
+// has waited for that group's EVAL, and the helpers take commands in order, so every helper is past it; behind that EVAL the group
+// before may have posted its EXPLAIN, its UNSCATTER and (streamed instance) its PUBLISH: 3. The group itself posts at most the next
+// group's SCATTER and EVAL, its own EXPLAIN, UNSCATTER and PUBLISH: 5. (A group that prepares the next one late — dep_prev — posts the
+// same commands in another order, and waits for none of them either.) The CPU-fiber build of the streamed instance asserts
+// posted - min(helper position) <= G2_RING at every post (G2_RING_CHECK, tests/emu/emu_groups_stream.cpp).
+#ifndef G2_RING_CHECK
+#define G2_RING_CHECK(posted) ((void)0)
+#endif
 WV_DEV void g2_post(G2Mail* mb, G2Post& P, u32 op, u32 gi) {
+    G2_RING_CHECK(P.n + 1u);
     if (wv::lane() == 0) {
         mb->op[P.n % G2_RING] = op;
         mb->grp[P.n % G2_RING] = gi;
@@ -1857,7 +1922,9 @@ WV_KERNEL(64) void k_g2_static(Groups2Args a) {
     if (wv::block() < a.n_scls) g2_static_list(a, wv::block());
 }
 
-WV_KERNEL(G2_THREADS) void k_groups2(Groups2Args a) {
+// One tick: the body of both instances of the kernel. PUB: the streamed one (G2Pub above).
+template <bool PUB>
+WV_DEV void g2_tick(const Groups2Args& a, const G2Pub& pb) {
     unsigned char* l = reinterpret_cast<unsigned char*>(wv::lds());
     G2Mail* mb = reinterpret_cast<G2Mail*>(l);
     G2Stage* sg = reinterpret_cast<G2Stage*>(l + 512);
@@ -1867,7 +1934,7 @@ WV_KERNEL(G2_THREADS) void k_groups2(Groups2Args a) {
     wv::barrier();
     if (a.ctl->error != ERR_NONE || a.n_groups == 0) return;
     if (wave != 0) {
-        g2_helper(a, mb, wave - 1u, nh);
+        g2_helper<PUB>(a, pb, mb, wave - 1u, nh);
         return;
     }
     g2_pre_table(reinterpret_cast<u64*>(l + G2_PRE_OFF), reinterpret_cast<u64*>(l + G2_LEFT_OFF));
@@ -1887,6 +1954,8 @@ WV_KERNEL(G2_THREADS) void k_groups2(Groups2Args a) {
     u32 eval_cur = P.n;
     bool ok = true;
     G2Pend X{0, 0, 0};
+    u32 pub_since = 0, pub_done = 0;   // the streamed instance: tasks decided since the last PUBLISH, groups gone through
+    (void)pub_since; (void)pub_done; (void)pb;
     for (u32 gi = 0; gi < a.n_groups && ok; ++gi) {
         if (!g2_wait_ge(&mb->done, eval_cur * nh, mb)) { ok = false; break; }
         if (wv::g_fresh32(&a.ctl->error) != ERR_NONE) { ok = false; break; }
@@ -1910,14 +1979,40 @@ WV_KERNEL(G2_THREADS) void k_groups2(Groups2Args a) {
         else if (in_lds) ok = g2_group<true, true>(a, mb, sg, l + G2_LDS_FIXED, G, gi, gt, gx, P, nh, eval_next, X);
         else ok = g2_group<false, true>(a, mb, sg, a.arena, G, gi, gt, gx, P, nh, eval_next, X);
         eval_cur = eval_next;
+#ifdef SWP_G2_STREAM
+        if constexpr (PUB) {
+            // the group's placements are stored and waited for (g2_group's write-back ends in wait_vm): they may go out. The rule the host
+            // knows (swp_rounds.hpp group_marks); the command is never waited for — the QUIT at the end is behind it in the ring.
+            if (ok) {
+                pub_done = gi + 1u;
+                pub_since += G.k;
+                if (pub_since >= pb.step || gi + 1u == a.n_groups) {
+                    g2_post(mb, P, G2_OP_PUBLISH, gi);
+                    pub_since = 0;
+                }
+            }
+        }
+#endif
         if (G2_PROF_ON(a)) tk = wv::clock64();
     }
     if (ok) ok = g2_take_explain(a, mb, X, nh);   // the last group's
     if (!ok && lane == 0) {
-        if (wv::lds_poll32(&mb->quit) && wv::g_fresh32(&a.ctl->error) == ERR_NONE) a.ctl->error = ERR_GROUP_HANG;
-        wv::lds_publish32(&mb->quit, 1u);   // helpers leave their wait loops
+        bool drain = false;
+#ifdef SWP_G2_STREAM
+        // a cancel: nothing is wrong between the waves — the helpers run the ring down to the QUIT below like at a tick's end
+        if constexpr (PUB) drain = wv::g_fresh32(&a.ctl->error) == ERR_GROUP_CANCELLED && !wv::lds_poll32(&mb->quit);
+#endif
+        if (!drain) {
+            if (wv::lds_poll32(&mb->quit) && wv::g_fresh32(&a.ctl->error) == ERR_NONE) a.ctl->error = ERR_GROUP_HANG;
+            wv::lds_publish32(&mb->quit, 1u);   // helpers leave their wait loops
+        }
     }
     g2_post(mb, P, G2_OP_QUIT, 0);
+#ifdef SWP_G2_STREAM
+    if constexpr (PUB) {
+        if (lane == 0) pb.d_stop[0] = pub_done;
+    }
+#endif
     if (lane == 0 && G2_PROF_ON(a)) {
         for (int q = 0; q < 8; ++q) a.ctl->cyc[q] = gt[q];
         a.ctl->m_cyc[0] = gt[8];   // inside the walk: orderedNodes ...
@@ -1929,6 +2024,12 @@ WV_KERNEL(G2_THREADS) void k_groups2(Groups2Args a) {
         for (int q = 0; q < 4; ++q) a.ctl->wave_cyc[8 + q] = gx[10 + q];   // admission: words visited, candidates staged, heap operations, cycles inside lane 0's replay
     }
 }
+
+WV_KERNEL(G2_THREADS) void k_groups2(Groups2Args a) { g2_tick<false>(a, G2Pub{}); }
+#ifdef SWP_G2_STREAM
+// the streamed instance: everything in this header that names a system-scope primitive sits behind SWP_G2_STREAM
+WV_KERNEL(G2_THREADS) void k_groups2s(Groups2Args a, G2Pub pb) { g2_tick<true>(a, pb); }
+#endif
 
 #endif   // SWP_G2_KERNELS
 }  // namespace swpdev

@@ -61,6 +61,8 @@ hipError_t launch_scan(const ScanArgs& s, hipStream_t st, int dev, bool node_loc
 // task groups (swp_groups.hip)
 struct Groups2Args;
 hipError_t launch_groups2(const Groups2Args& a, hipStream_t s, int dev);
+struct G2Pub;
+hipError_t launch_groups2_streamed(const Groups2Args& a, const G2Pub& pb, hipStream_t s, int dev);   // k_groups2s
 
 // runs of identical tasks (swp_waterfill.hip)
 struct WaterArgs;

@@ -122,4 +122,37 @@ struct StreamMarks {
     bool complete() const { return !bad && delivered == T; }       // after the last mark: every task went out exactly once
 };
 
+// The streamed tick of task groups (swp_schedule_groups_streamed): ONE launch decides group after group, and the kernel itself appends
+// the marks (swp_groups.hpp G2_OP_PUBLISH) — there is nothing between rounds where the host could drain the ring, and the kernel never
+// waits for the host. So the rule is one the host can compute up front from the sizes alone: a mark behind group g iff the groups since
+// the previous mark hold at least `step` tasks, or g is the last group. A tick never has more marks than groups; one of more than
+// RING / 2 groups gets a step of at least total / (RING / 2), rounded up: a tick's marks then fill at most half the ring, whatever
+// the knob says.
+inline uint32_t stream_group_tasks() {   // SWP_STREAM_GROUP_TASKS: tasks between two marks of a streamed tick, at least (default 1024)
+    const char* env = getenv("SWP_STREAM_GROUP_TASKS");
+    const long long v = env ? atoll(env) : 1024;
+    return (uint32_t)std::min<long long>(std::max<long long>(v, 1), 0x7FFFFFFF);
+}
+inline uint32_t group_pub_step(uint64_t total, uint32_t n_groups, uint32_t knob) {
+    const uint64_t half = StreamMarks::RING / 2;
+    const uint64_t floor_ = n_groups > half ? (total + half - 1) / half : 1;
+    return (uint32_t)std::max<uint64_t>(std::max<uint32_t>(knob, 1u), floor_);
+}
+inline bool group_mark_due(uint32_t since, uint32_t step, bool last) { return since >= step || last; }   // (the kernel's test, word for word)
+// on_mark(mark, group) for every mark of the tick, in order; returns how many there are
+template <class F>
+inline uint32_t group_marks(const uint32_t* sizes, uint32_t n_groups, uint32_t step, F on_mark) {
+    uint32_t marks = 0, since = 0, end = 0;
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        since += sizes[g];
+        end += sizes[g];
+        if (group_mark_due(since, step, g + 1 == n_groups)) {
+            on_mark(end, g);
+            since = 0;
+            ++marks;
+        }
+    }
+    return marks;
+}
+
 }  // namespace swpdev

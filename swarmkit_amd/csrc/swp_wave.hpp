@@ -137,6 +137,13 @@ WV_DEV void g_max32(u32* p, u32 v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAX
 WV_DEV u64 g_fresh64(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV u32 g_fresh32(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 WV_DEV i64 g_fresh64s(const i64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// ---- system scope: words a HOST polls while the kernel runs (fine-grained pinned memory; k_groups2's streamed instance) ----
+// Agent scope ends at this device's L2 and the host is outside it. sys_fence: the wave's stores so far are released to the host;
+// a word stored behind it (relaxed), then the counter the host acquires (release) — k_publish's order (swp_publish.hpp).
+WV_DEV void sys_fence() { __threadfence_system(); }
+WV_DEV void sys_store32(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+WV_DEV void sys_store_release32(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+WV_DEV u32 sys_load32(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 // pull the cache line at p into this XCD's L2. An ordinary load whose value the caller must consume (sum it up and hand the
 // sum to keep()): the compiler then orders the wait itself. (A bare global_load in inline asm returns into a register the
 // compiler believes free — the late write corrupted whatever lived there next: found by the 12 400-node scan-mode case.)

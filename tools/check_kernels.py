@@ -26,6 +26,7 @@ SCRATCH_OK = {
     "k_r6_commit_v": "vol_choose's per-mount arrays (the only block-resolver instance with cluster mounts)",
     "k_r7_commit_v": "the same, sharded",
     "k_groups2": "three inlined instances of one group's machine: SGPR spills to VGPR lanes, 192 B of timers and frames",
+    "k_groups2s": "the same kernel's streamed instance (swp_schedule_groups_streamed): one more command for the helpers",
     "k_explain": "per-task Explain of tasks with generic reservations / mounts: small per-thread arrays",
     "k_vol_choose": "chooseTaskVolumes for one pair: per-mount arrays",
     "k_r6_volrows": "per-mount arrays",
@@ -33,8 +34,9 @@ SCRATCH_OK = {
 # 1024-thread kernels allowed above 120 VGPRs
 VGPR_EDGE_OK = {
     "k_groups2": "one workgroup per launch: the machine wave's three instances; no VGPR spills beyond the listed 4 is checked below",
+    "k_groups2s": "the same kernel's streamed instance",
 }
-VGPR_SPILL_OK = {"k_groups2": 12}    # (orderedNodes' second hand-out: swap-based moves of 16-byte records — rare paths; checked in the disassembly)
+VGPR_SPILL_OK = {"k_groups2": 12, "k_groups2s": 12}    # (orderedNodes' second hand-out: swap-based moves of 16-byte records — rare paths; checked in the disassembly)
 
 
 def demangle_short(name):
