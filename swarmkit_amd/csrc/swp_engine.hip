@@ -573,7 +573,7 @@ struct swp_engine {
     void* rccl_comm = nullptr;
     uint32_t rccl_rank = 0, rccl_ranks = 0;
 
-    std::vector<hipEvent_t> ev_scan;   // SWP_CFG_PROFILE: a pair per stretch the scan resolver took (run_blocks); ev_scan_used of them in this batch
+    std::vector<hipEvent_t> ev_scan;   // SWP_CFG_PROFILE: a pair per stretch the scan resolver took (scan_stretch); ev_scan_used of them in this batch
     uint32_t ev_scan_used = 0, scan_tasks_batch = 0, scan_stretches_batch = 0;
     bool r6_compact_hint = false;   // the last batch's rounds used a compact index (re-placements after a drain): the next one starts with it
     swp_stats_t stats{};
@@ -1215,7 +1215,7 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
     b->n_plug = (uint32_t)plug_ids.size();
 
     b->tmpl = std::move(tmpl_of);
-    {   // tasks that stand in a run of >= 8 identical tasks: the length from which the commit kernel takes a run's picks by rank (run_blocks)
+    {   // tasks that stand in a run of >= 8 identical tasks: the length from which the commit kernel takes a run's picks by rank (swp_rounds.hpp r6_shape)
         uint32_t in_runs = 0;
         for (uint32_t i = 0, j; i < T; i = j) {
             for (j = i + 1; j < T && b->tmpl[j] == b->tmpl[i]; ++j) {}
@@ -1762,7 +1762,7 @@ int batch_begin(swp_engine* e, swp_batch* b) {
 
 // The block resolver's argument record for (engine, batch): reserves the buffers it names. task_rows: ResourceFilter rows per task of
 // the block instead of per demand class (swp_resolve6.hpp k_r6_taskrows).
-int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_rows, uint32_t dbg_bits, R6Args* out) {
+int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_rows, const R6Knobs& knobs, R6Args* out) {
     const uint32_t N = e->n_nodes, Wn = n_words_of(N);
     const uint32_t r6_nrr = r6_task_rows ? 0u : b->n_dc + b->n_dm;
     HIPCHECK(e, b->d_planes6.reserve((size_t)R6_NP * Wn * 8));
@@ -1770,7 +1770,7 @@ int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_row
     if (r6_task_rows) HIPCHECK(e, b->d_trows.reserve((size_t)r6_block * Wn * 8));
     HIPCHECK(e, b->d_blk6.reserve(sizeof(Blk6)));
     HIPCHECK(e, b->d_prop.reserve(r7_send_bytes(r6_block)));   // (the shard drivers send two trailer slots behind the block: swp_resolve7.hpp)
-    if (Wn <= R6_COMPACT_MAX_WORDS) {   // the compact index of a round (k_r6_compact); run_blocks switches it on
+    if (Wn <= R6_COMPACT_MAX_WORDS) {   // the compact index of a round (k_r6_compact); swp_rounds.hpp CompactSwitch switches it on
         HIPCHECK(e, b->d_cmask.reserve((size_t)Wn * 8));
         HIPCHECK(e, b->d_crank.reserve((size_t)Wn * 4));
         HIPCHECK(e, b->d_cidx.reserve((size_t)r6_compact_cap(Wn) * 4));
@@ -1784,7 +1784,7 @@ int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_row
     ra.n_dm = r6_task_rows ? 0u : b->n_dm;
     ra.task_rows = r6_task_rows ? 1u : 0u;
     ra.trows = r6_task_rows ? b->d_trows.as<u64>() : nullptr;
-    ra.dbg = dbg_bits;
+    ra.dbg = knobs.dbg;
     ra.no_runs = b->tasks_in_runs == 0 ? 1u : 0u;   // (round-robin batches: nothing for the matcher's runs-by-rank path to find)
     ra.valid = e->d_valid.as<u64>();
     ra.sc = b->d_sc.as<u64>();
@@ -1824,10 +1824,7 @@ int r6_args_for(swp_engine* e, swp_batch* b, uint32_t r6_block, bool r6_task_row
         ra.att = b->d_att.as<uint32_t>();
         ra.vol = vol_view(e);
     }
-    {   // SWP_R6_TWINS=0: every list starts at its level's first candidate (A/B runs)
-        const char* env_tw = getenv("SWP_R6_TWINS");
-        ra.tmpl = (env_tw && atoi(env_tw) == 0) ? nullptr : b->d_tmpl.as<uint32_t>();
-    }
+    ra.tmpl = knobs.twins ? b->d_tmpl.as<uint32_t>() : nullptr;   // SWP_R6_TWINS=0: every list starts at its level's first candidate (A/B runs)
     if (b->has_generic) {
         HIPCHECK(e, b->d_rg.reserve((size_t)b->rg_kind.size() * Wn * 8));
         ra.n_rg = (u32)b->rg_kind.size();
@@ -1894,247 +1891,294 @@ int batch_run(swp_engine* e, swp_batch* b) {
     return rc;
 }
 
+// ---- the single engine's rounds: the steps of batch_run_impl. The RULES (knobs, runs and window, block, pace, compact switch, scan
+// hand-over) are swp_rounds.hpp's; here are the mechanics: launches, read-backs, events, reports, counters. -------------------------
 // sx != nullptr: the streamed variant — the same launches, the same pace and knobs, with a publish behind every stream_rounds(sx)
 // rounds, every scan stretch and every k_waterfill run; where the plain driver waits for the stream, this one polls an event and hands
 // the marks that arrived to the sink meanwhile (stream_wait). A non-zero code of those steps ends the pass like any other failure.
+
+struct R6Run {   // what a run decides once and its stretches share
+    StreamRun* sx;
+    bool prof;
+    R6Knobs knobs;
+    R6Shape shape;
+    bool task_rows;
+    uint32_t nrr, block;   // demand-class rows in the commit kernel's LDS; the largest block it holds next to them
+    uint32_t wi = 0;       // resolver stretches launched so far (profiling slots)
+    uint64_t rounds = 0;
+};
+struct R6Stretch {   // one stretch [start, end) of k_resolve6's rounds: what its steps share
+    uint32_t start, end;
+    R6Args ra;
+    RoundRules rules;   // pace, compact switch, scan hand-over
+    Blk6 hb{};          // the control block as last read
+};
+R6Words r6_words(const Blk6& hb) { return R6Words{hb.pos, hb.rounds, hb.cut_exhausted + hb.cut_window, hb.crounds, hb.reseats, hb.scan_skipped}; }
+
+// k_resolve6, the BLOCK resolver: lists built by the whole chip from bitmap rows in global memory, matched by one wave. Needs the
+// demand classes and two candidate buffers of the propose kernel in LDS (≈ 650k nodes). Without SWP_R6_BLOCK: as many 64-task groups
+// as the commit kernel's LDS holds next to the TK row, at most R6_BLOCK_DEFAULT_CAP tasks.
+int r6_run_plan(swp_engine* e, swp_batch* b, R6Run* run) {
+    const uint32_t Wn = n_words_of(e->n_nodes);
+    run->knobs = r6_knobs(r6_block_max(), R6_BLOCK_DEFAULT_CAP);
+    run->task_rows = swpdev::r6_task_rows(run->knobs, b->classes_ok, b->n_dc + b->n_dm);
+    run->shape = r6_shape(run->knobs, b->tasks_in_runs, b->T);
+    const uint32_t nrr = run->nrr = run->task_rows ? 0u : b->n_dc + b->n_dm, win = run->shape.win;
+    // (where a compact index may be built, the block leaves the room for its quarter more of TK row)
+    const bool cpt_room = Wn <= R6_COMPACT_MAX_WORDS && b->csi_set.empty();
+    run->block = r6_fit_block(run->shape.cap, [&](uint32_t bl) { return r6_commit_lds_size(Wn, bl, nrr, cpt_room, win); });
+    if (r6_propose_lds_size(Wn) > R6_LDS_BUDGET || r6_commit_lds_size(Wn, run->block, nrr, false, win) > R6_LDS_BUDGET || Wn > 32768u)   // (half-word indices of 16 bits in the commit kernel's LDS)
+        return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", e->n_nodes);
+    return SWP_OK;
+}
+
+// `bytes` of device memory behind the stream's work so far. Streamed: through the batch's pinned words — a copy into pageable memory
+// may hold the host until the stream is through, and the marks are serviced while the host waits, not before (drain: every mark).
+int read_back(swp_engine* e, swp_batch* b, StreamRun* sx, const void* src, void* dst, size_t bytes, bool drain = false) {
+    HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (!sx) {
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        return SWP_OK;
+    }
+    if (int rc = stream_wait(e, sx, drain)) return rc;
+    std::memcpy(dst, b->h_words.p, bytes);
+    return SWP_OK;
+}
+
+int grow_events(swp_engine* e, std::vector<hipEvent_t>& pool, size_t n) {
+    while (pool.size() < n) {
+        hipEvent_t x;
+        HIPCHECK(e, hipEventCreate(&x));
+        pool.push_back(x);
+    }
+    return SWP_OK;
+}
+
+// `chunk` rounds: in one piece, or streamed in pieces with a publish behind each (the last piece included: a stretch ends published)
+int launch_chunk(swp_engine* e, swp_batch* b, StreamRun* sx, const R6Args& ra, uint32_t chunk) {
+    for (uint32_t done = 0; done < chunk;) {
+        const uint32_t piece = sx ? std::min<uint32_t>(stream_rounds(sx), chunk - done) : chunk;
+        const hipError_t r = launch_r6_rounds(ra, piece, e->stream, e->device);
+        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 round launch: %s", hipGetErrorString(r));
+        done += piece;
+        if (sx)
+            if (int rc = stream_publish(e, sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rc;
+    }
+    return SWP_OK;
+}
+
+// The tasks [pos, upto) to the scan resolver, one after the other (swp_scan.hpp); behind it the bitmaps rebuilt — the rounds go on from
+// the rows as the scan left them — and, streamed, a publish (the scan kernels leave Blk6.pos at the end of their stretch).
+// *node_local: k_scanb could take it (every input of a task in LDS, every effect on ONE node).
+int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t pos, uint32_t upto, bool* node_local) {
+    hipStream_t st = e->stream;
+    ScanArgs sa{};
+    sa.a = ra;
+    sa.j0 = pos;
+    sa.j1 = upto;
+    sa.n_svc = b->n_svc;
+    HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * e->n_nodes * 4));
+    HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * e->n_nodes * 4));
+    sa.hmat = b->d_hmat.as<uint32_t>();
+    sa.emat = b->d_emat.as<uint32_t>();
+    sa.n_sc = b->n_sc;
+    bool local = ra.n_rg == 0 && ra.csi_of == nullptr;
+    for (uint32_t j = pos; j < upto && local; ++j)
+        if (b->rt[j].flags & RT_PORTS) local = false;
+    *node_local = local;
+    if (run.prof) {
+        if (int rc = grow_events(e, e->ev_scan, (size_t)e->ev_scan_used + 2)) return rc;
+        HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used], st));
+    }
+    hipError_t r = launch_scan(sa, st, e->device, local);
+    if (run.prof) {
+        HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used + 1], st));
+        e->ev_scan_used += 2;
+    }
+    e->scan_tasks_batch += upto - pos;
+    e->scan_stretches_batch += 1;
+    if (r == hipSuccess) r = launch_r6_build(ra, st);
+    if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan launch: %s", hipGetErrorString(r));
+    if (run.sx)
+        if (int rc = stream_publish(e, run.sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rc;
+    return SWP_OK;
+}
+
+// SWP_DBG=16: the commit kernel's section timers of a control block, per round. sharded: k_r7_commit's, which folds in its prologue and
+// has no wave waiting for the matcher.
+void r6_report(const Blk6& hb, bool sharded) {
+    const double rr_ = std::max<uint32_t>(hb.rounds, 1);
+    char wait[64] = "";
+    if (!sharded) snprintf(wait, sizeof wait, "the others' wait for it %.0f, ", hb.cyc[2] * 64.0 / rr_);
+    fprintf(stderr, "[swp] %s shader cycles per round: %s %.0f, matching (wave 0) %.0f (list loads %.0f, walks %.0f), %sapply %.0f | %.1f matcher stops at an emptied half-word per round\n",
+            sharded ? "k_r7_commit (shard 0)" : "k_r6_commit", sharded ? "prologue + fold" : "prologue", hb.cyc[0] * 64.0 / rr_, hb.cyc[1] * 64.0 / rr_, hb.cyc_load * 64.0 / rr_,
+            hb.cyc_walk * 64.0 / rr_, wait, hb.cyc[3] * 64.0 / rr_, hb.reseats / rr_);
+    fprintf(stderr, "[swp] ... of the list loads: waiting for a group's lists %.0f, its head records %.0f, seating %.0f (%.1f steps of the seating loop, stops included) per round\n", hb.cyc_g[0] * 64.0 / rr_,
+            hb.cyc_g[1] * 64.0 / rr_, hb.cyc_g[2] * 64.0 / rr_, hb.cyc_g[3] / rr_);
+    fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hb.cyc_h[0] * 64.0 / rr_, hb.cyc_h[1] * 64.0 / rr_,
+            hb.cyc_h[2] * 64.0 / rr_);
+    fprintf(stderr, "[swp] ... of the walks and behind them: inside the walk %.0f (%.1f calls), the stops %.0f, a group's epilogue (last walk to publish) %.0f per round\n", hb.cyc_s[0] * 64.0 / rr_, hb.dbg_walks / rr_,
+            hb.cyc_s[1] * 64.0 / rr_, hb.cyc_s[2] * 64.0 / rr_);
+}
+
+// SWP_DBG=16: what a stretch's control block says at its end
+void stretch_report(swp_batch* b, const R6Run& run, const R6Stretch& s) {
+    const Blk6& hb = s.hb;
+    const uint32_t scanned = s.rules.scan.scanned;
+    if (scanned) fprintf(stderr, "[swp] k_scan decided %u tasks of [%u, %u), %u of them without a look (an identical task had found no node), the others %.2f to a barrier\n", scanned, s.start, s.end, hb.scan_skipped, (double)(scanned - hb.scan_skipped) / std::max(1u, hb.scan_batches));
+#ifdef SWP_SCAN_PROF
+    if (scanned) {
+        Ctl pc{};
+        (void)hipMemcpy(&pc, b->d_ctl.p, sizeof pc, hipMemcpyDeviceToHost);
+        const double nb_ = std::max(1u, hb.scan_batches);
+        fprintf(stderr, "[swp] k_scanb cycles per batch (wave 0; %u batches): read + evaluate %.0f, reduce + atomic %.0f, barrier %.0f, accept %.0f, apply %.0f, window work %.0f\n", hb.scan_batches,
+                pc.cyc[0] / nb_, pc.cyc[1] / nb_, pc.cyc[2] / nb_, pc.cyc[3] / nb_, pc.cyc[4] / nb_, pc.cyc[5] / nb_);
+    }
+#endif
+    if (hb.crounds) fprintf(stderr, "[swp] %u of the %u rounds with a compact index | of the cuts at an exhausted list: %u full lists, %u lists in compact positions, %u lists of one entry\n", hb.crounds, hb.rounds, hb.dbg_cut[0], hb.dbg_cut[1], hb.dbg_cut[2]);
+    fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, a window that ran out %u, an exception-list task %u, an uncounted task %u\n", s.start, s.end,
+            hb.rounds, run.block, (double)(s.end - s.start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted);
+    r6_report(hb, false);
+}
+
+// What the engine and the batch allow the rules of a stretch: no compact index that would need a smaller block, nor with volumes; the
+// scan resolver knows no volumes, and its keys hold 255 failures and 2^24 - 1 tasks of a service on a node; its batched instance
+// (k_scanb) knows no generic resources either, and a window's rows must fit its LDS.
+RoundRules stretch_rules(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t start, uint32_t end) {
+    const uint32_t N = e->n_nodes, Wn = n_words_of(N);
+    const bool cpt_allowed = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, run.block, run.nrr, true, run.shape.win) <= R6_LDS_BUDGET && b->csi_set.empty();
+    const bool scan_ok = N <= scan_max_nodes() && run.knobs.scan && b->csi_set.empty() && !b->wide_keys;
+    const bool scan_fast = ra.n_rg == 0 && ra.csi_of == nullptr && scan_batched_fits(N, b->n_svc, b->n_sc);
+    return RoundRules{RoundPace(end - start, run.block, run.knobs.block_forced, start), CompactSwitch(cpt_allowed, run.knobs, e->r6_compact_hint), ScanHandover(scan_ok, scan_fast), !run.shape.runs};
+}
+
+// On the stream: the stretch's position and end, the bitmaps built from the node rows as they are.
+int stretch_begin(swp_engine* e, swp_batch* b, const R6Run& run, R6Stretch& s) {
+    hipStream_t st = e->stream;
+    // lists of R6_LIST half-words, the entries behind a proposal's 32 (RoundRules::ext: only for full-size blocks of ordinary batches.
+    // Wave 0 of every propose workgroup pays for listing them, and neither a batch of runs nor rounds that are cut after a few dozen
+    // tasks get anything for it: service-major cfg3 and the churn rounds were slower with them)
+    HIPCHECK(e, b->d_ext.reserve((size_t)run.block * sizeof(R6PropExt)));
+    s.ra.ext = s.rules.ext() ? b->d_ext.as<R6PropExt>() : nullptr;
+    s.ra.win = run.shape.win;
+    if (run.prof) {
+        if (int rc = grow_events(e, e->ev_pool, (size_t)4 * (run.wi + 1))) return rc;
+        for (uint32_t q = 0; q < 3; ++q) HIPCHECK(e, hipEventRecord(e->ev_pool[4 * run.wi + q], st));
+    }
+    s.hb.pos = s.start;
+    s.hb.end = s.end;
+    HIPCHECK(e, hipMemcpyAsync(b->d_blk6.p, &s.hb, sizeof s.hb, hipMemcpyHostToDevice, st));
+    const hipError_t r = launch_r6_build(s.ra, st);
+    if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 build launch: %s", hipGetErrorString(r));
+    return SWP_OK;
+}
+
+// k_resolve6 over the stretch [start, end): rounds of propose + commit, enqueued blindly a chunk at a time. The device advances on its
+// own (the position lives in the control block); the host only learns every so many rounds how far it is, and asks the rules.
+int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_t end) {
+    R6Args ra{};
+    if (int rc = r6_args_for(e, b, run.block, run.task_rows, run.knobs, &ra)) return rc;
+    R6Stretch s{start, end, ra, stretch_rules(e, b, run, ra, start, end)};
+    if (int rc = stretch_begin(e, b, run, s)) return rc;
+    RoundPace& pace = s.rules.pace;
+    Blk6& hb = s.hb;
+    const uint32_t dbg_bits = run.knobs.dbg;
+    while (pace.pos < end) {
+        s.ra.block = pace.block;
+        s.ra.compact = s.rules.cpt.compact();
+        s.ra.ext = s.rules.ext() ? b->d_ext.as<R6PropExt>() : nullptr;
+        if (int rc = launch_chunk(e, b, run.sx, s.ra, pace.chunk)) return rc;
+        if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
+        if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
+        if (hb.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the %d level planes of the block resolver", R6_NP);
+        if (hb.pos <= pace.pos) return e->fail(SWP_EHIP, "block resolver made no progress at task %u", pace.pos);   // a round decides its first task at least
+        uint32_t used;   // rounds that found work
+        double recent;
+        bool to_scan = s.rules.after_rounds(r6_words(hb), &used, &recent);
+        if (dbg_bits & 32) fprintf(stderr, "[swp] chunk: %u rounds, %.1f tasks each, at %u of %u | block %u compact %u csize %u clevel %u base %u maxrel %u\n", used, recent, pace.pos, end, s.ra.block, s.ra.compact, hb.csize, hb.clevel, hb.base, hb.maxrel);
+        while (to_scan) {   // a scan stretch, and another directly behind it while the rules say so
+            const uint32_t upto = s.rules.scan_upto();
+            bool node_local = false;
+            if (int rc = scan_stretch(e, b, run, s.ra, pace.pos, upto, &node_local)) return rc;
+            const bool looks = s.rules.scan.looks(node_local, upto, end, (dbg_bits & 16) != 0);
+            if (looks)
+                if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
+            const R6Words w = r6_words(hb);
+            to_scan = s.rules.after_scan(upto, looks ? &w : nullptr);
+        }
+    }
+    e->r6_compact_hint = s.rules.cpt.ever;
+    run.rounds += hb.rounds;
+    if (run.prof) HIPCHECK(e, hipEventRecord(e->ev_pool[4 * run.wi + 3], e->stream));
+    ++run.wi;
+    if (dbg_bits & 16) stretch_report(b, run, s);
+    return SWP_OK;
+}
+
+// SWP_CFG_PROFILE: the phases' and the stretches' events into the stats
+int batch_profile(swp_engine* e, swp_batch* b, const R6Run& run) {
+    HIPCHECK(e, hipEventRecord(e->ev[3], e->stream));
+    HIPCHECK(e, hipEventSynchronize(e->ev[3]));
+    auto ms = [](hipEvent_t from, hipEvent_t to) {
+        float x = 0;
+        (void)hipEventElapsedTime(&x, from, to);
+        return x;
+    };
+    float scan_sum = 0, res_sum = 0;
+    for (uint32_t q = 0; q < run.wi; ++q) {
+        scan_sum += ms(e->ev_pool[4 * q + 0], e->ev_pool[4 * q + 1]);
+        res_sum += ms(e->ev_pool[4 * q + 2], e->ev_pool[4 * q + 3]);
+    }
+    for (uint32_t q = 0; q + 1 < e->ev_scan_used; q += 2) scan_sum += ms(e->ev_scan[q], e->ev_scan[q + 1]);   // the stretches the scan resolver took (k_scan_fill + k_scan_lists + k_scan / k_scanb each)
+    e->stats.ms_classes = ms(e->ev[0], e->ev[1]);
+    e->stats.ms_scan = scan_sum;      // Σ over windows of k_scan launch durations
+    e->stats.ms_resolve = b->segs.empty() ? res_sum : ms(e->ev[1], e->ev[2]);   // Σ of the resolver launches; with runs of identical tasks in the batch: the whole phase (k_waterfill launches + the stretches between them)
+    e->stats.ms_explain = ms(e->ev[2], e->ev[3]);
+    e->stats.ms_total = ms(e->ev[0], e->ev[3]);
+    return SWP_OK;
+}
+
+void batch_stats(swp_engine* e, swp_batch* b, const R6Run& run, const Ctl& ctl) {
+    e->stats.verify_retries += ctl.verify_retries;
+    e->stats.slow_path_tasks += ctl.slow_tasks;
+    e->stats.rebase_events += ctl.rebases;
+    e->stats.generic_tasks += ctl.generic_tasks;
+    e->stats.resolver_spins += ctl.spin_waits;
+    if (run.knobs.dbg & 16)
+        fprintf(stderr, "[swp] resolver cycles (100MHz ticks): wait %llu prep %llu pick %llu generic %llu commit %llu blockend %llu | commits %u inf %u generic %llu\n",
+                ctl.cyc[0], ctl.cyc[1], ctl.cyc[2], ctl.cyc[3], ctl.cyc[4], ctl.cyc[5], ctl.ncommit, ctl.ninf, ctl.generic_tasks);
+    if ((run.knobs.dbg & 16) && ctl.cyc[7])
+        fprintf(stderr, "[swp] shader clock: %llu cycles / %llu x10ns => %.0f MHz\n", ctl.cyc[6], ctl.cyc[7], (double)ctl.cyc[6] / ((double)ctl.cyc[7] * 0.01));
+    e->stats.scan_launches = e->scan_stretches_batch;
+    e->stats.scan_tasks = e->scan_tasks_batch;
+    e->stats.last_windows = run.wi;   // resolver stretches of this batch
+    e->stats.last_static_classes = b->n_sc;
+    e->stats.resolve_launches += (uint32_t)(2 * run.rounds);   // k_resolve6: a propose and a commit launch per round
+    e->stats.last_resolver = 6u;   // k_resolve6
+}
+
+// begin; the stretches of k_resolve6's rounds with the k_waterfill runs between them; explain; stats
 int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     if (e->n_nodes != b->n_nodes_prepared)
         return e->fail(SWP_EINVAL, "the nodeSet grew from %u to %u node slots since swp_batch_prepare: prepare the batch again", b->n_nodes_prepared, e->n_nodes);
-    const uint32_t N = e->n_nodes, Wn = n_words_of(N), T = b->T;
+    const uint32_t N = e->n_nodes, T = b->T;
     if (N == 0 || T == 0) { b->ran = true; return SWP_OK; }
-    const bool prof = (e->cfg.flags & SWP_CFG_PROFILE) != 0;
+    R6Run run{sx, (e->cfg.flags & SWP_CFG_PROFILE) != 0};
     hipStream_t st = e->stream;
-    if (prof) HIPCHECK(e, hipEventRecord(e->ev[0], st));
+    if (run.prof) HIPCHECK(e, hipEventRecord(e->ev[0], st));
     e->ev_scan_used = 0;
     e->scan_tasks_batch = e->scan_stretches_batch = 0;
 
     int rc = batch_begin(e, b);
     if (rc) return rc;
-    if (prof) HIPCHECK(e, hipEventRecord(e->ev[1], st));
-
-    // k_resolve6, the BLOCK resolver: lists built by the whole chip from bitmap rows in global memory, matched by one wave. Needs the
-    // demand classes and two candidate buffers of the propose kernel in LDS (≈ 650k nodes). Knobs, row mode and block: swp_rounds.hpp
-    // (without SWP_R6_BLOCK: as many 64-task groups as the commit kernel's LDS holds next to the TK row, at most R6_BLOCK_DEFAULT_CAP tasks).
-    const R6Knobs knobs = r6_knobs(r6_block_max(), R6_BLOCK_DEFAULT_CAP);
-    const uint32_t dbg_bits = knobs.dbg;
-    const bool r6_task_rows = swpdev::r6_task_rows(knobs, b->classes_ok, b->n_dc + b->n_dm);
-    const uint32_t r6_nrr = r6_task_rows ? 0u : b->n_dc + b->n_dm;
-    // (where a compact index may be built, the block leaves the room for its quarter more of TK row)
-    const bool r6_cpt_room = Wn <= R6_COMPACT_MAX_WORDS && b->csi_set.empty();
-    // A batch that is mostly RUNS of identical tasks (service-major order) keeps whole proposals in LDS and the blocks they allow: the
-    // runs-by-rank path (runs of >= 8) takes a run's picks from ONE task's window, and with windows of 16 in blocks of 1 408 service-major
-    // cfg3 — every task in a run of 100 — took 327 rounds and 12.6 ms where the parent took 288 and 10.2 (profiles/late_window.json,
-    // "major_windows_of_16"). Measured at the two ends only — no task in such a run (the headline), every task in one; the line between
-    // them is drawn at half the batch's tasks, counted once when the batch is built. SWP_R6_RUNS=0 / 1 forces either (tests, A/B runs);
-    // SWP_R6_BLOCK still forces the block.
-    const char* env_runs = getenv("SWP_R6_RUNS");
-    const bool r6_runs = env_runs ? atoi(env_runs) != 0 : 2u * (uint64_t)b->tasks_in_runs > T;
-    const uint32_t r6_win = r6_runs ? 32u : 0u;
-    const uint32_t r6_cap = (r6_runs && !knobs.block_forced) ? std::min<uint32_t>(knobs.block_cap, 768u) : knobs.block_cap;
-    const uint32_t r6_block = r6_fit_block(r6_cap, [&](uint32_t bl) { return r6_commit_lds_size(Wn, bl, r6_nrr, r6_cpt_room, r6_win); });
-    const bool r6_ok = r6_propose_lds_size(Wn) <= R6_LDS_BUDGET && r6_commit_lds_size(Wn, r6_block, r6_nrr, false, r6_win) <= R6_LDS_BUDGET && Wn <= 32768u;   // (half-word indices of 16 bits in the commit kernel's LDS)
-    if (!r6_ok) return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", N);
-    uint32_t wi = 0;   // resolver stretches launched so far (profiling slots)
-    uint64_t r6_rounds = 0;
-    // k_resolve6 over the stretch [start, end): build the bitmaps from the node rows as they are, then rounds of propose + commit.
-    // The device advances on its own (the position lives in the control block); the host only learns every so many rounds how far it is.
-    auto run_blocks = [&](uint32_t start, uint32_t end) -> int {
-        if (prof)
-            while (e->ev_pool.size() < (size_t)4 * (wi + 1)) {
-                hipEvent_t x;
-                HIPCHECK(e, hipEventCreate(&x));
-                e->ev_pool.push_back(x);
-            }
-        R6Args ra{};
-        if (int rc6 = r6_args_for(e, b, r6_block, r6_task_rows, dbg_bits, &ra)) return rc6;
-        HIPCHECK(e, b->d_ext.reserve((size_t)r6_block * sizeof(R6PropExt)));   // lists of R6_LIST half-words: the entries behind a proposal's
-        // (lists beyond a proposal's 32 entries only for full-size blocks of ordinary batches: wave 0 of every propose workgroup pays for
-        // listing them, and neither a batch of runs — its windows hold a whole proposal — nor rounds that are cut after a few dozen
-        // tasks, whose block the pace has shrunk, get anything for it: service-major cfg3 and the churn rounds were slower with them)
-        R6PropExt* const r6_ext = r6_runs ? nullptr : b->d_ext.as<R6PropExt>();
-        ra.ext = r6_ext;
-        ra.win = r6_win;
-        if (prof) {
-            HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 0], st));
-            HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 1], st));
-            HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 2], st));
-        }
-        Blk6 hb{};
-        hb.pos = start;
-        hb.end = end;
-        HIPCHECK(e, hipMemcpyAsync(b->d_blk6.p, &hb, sizeof hb, hipMemcpyHostToDevice, st));
-        hipError_t r = launch_r6_build(ra, st);
-        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 build launch: %s", hipGetErrorString(r));
-        RoundPace pace(end - start, r6_block, knobs.block_forced, start);
-        uint32_t& pos = pace.pos;
-        uint32_t scan_len = 2048, scanned = 0, skipped_seen = 0;
-        bool after_scan = false;   // the rounds since the last scan stretch: four of them say whether the tasks still have no plain candidates
-        // The compact index (swp_resolve6.hpp, R6Args.compact): one more small launch per round, worth it when the level the tasks aim at is a
-        // sparse set of nodes (re-placements after a drain): the matcher then stops at an emptied half-word every few tasks and the rounds are
-        // cut by exhausted lists after a fraction of their block. Switched on by that symptom (a stop per <= 12 decided tasks; ordinary
-        // batches have one per 30-40), off again when the kernel found no such level in a whole chunk; the next batch starts the way this
-        // one ended if the index was in use then.
-        // SWP_R6_COMPACT=0 never, 1 from the first round on (tests, A/B runs).
-        const char* env_cpt = getenv("SWP_R6_COMPACT");
-        const bool cpt_ok = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, r6_block, r6_nrr, true, r6_win) <= R6_LDS_BUDGET && b->csi_set.empty() && !(env_cpt && atoi(env_cpt) == 0);   // (no smaller blocks for it)
-        bool cpt = cpt_ok && ((env_cpt && atoi(env_cpt) != 0) || e->r6_compact_hint);
-        // (the index of the NEXT round built at the end of k_r6_commit_c instead of by a launch of its own: SWP_R6_COMPACT_FUSED=0 for A/B runs)
-        const char* env_cf = getenv("SWP_R6_COMPACT_FUSED");
-        const bool cpt_fused = !(env_cf && atoi(env_cf) == 0);
-        bool cpt_ever = false;          // some chunk of this batch had rounds with an index
-        // (round 6: a churn round's batch ENDS on tasks that aim at a level every node has — no index — and the hint used to say "the last
-        // chunk had one": every batch then began with sixteen rounds without it. Starting with the previous batch's small BLOCK as well was
-        // measured and lost: device 3.39 -> 3.62 ms a round, same box, three runs each.)
-        uint32_t exh_seen = 0, crounds_seen = 0, stops_seen = 0;
-        const char* env_scan = getenv("SWP_SCAN");   // 0: never hand a stretch to the scan resolver (tests, A/B runs)
-        const bool scan_ok = N <= scan_max_nodes() && !(env_scan && atoi(env_scan) == 0) && b->csi_set.empty() && !b->wide_keys;   // (the scan resolver knows no volumes, and its keys hold 255 failures and 2^24 - 1 tasks of a service on a node)
-        // The batched instance of the scan (k_scanb) decides ~4 tasks a barrier and answers an unplaceable task's twins without a look: where
-        // it can run, a stretch goes to it after four poor rounds and two probing rounds follow it; the one-task-a-barrier instance
-        // (~1 us a task) has to be worth more: eight poor rounds, four probes
-        const bool scan_fast = scan_ok && ra.n_rg == 0 && ra.csi_of == nullptr && scan_batched_fits(N, b->n_svc, b->n_sc);
-        while (pos < end) {
-            ra.compact = cpt ? (cpt_fused ? 2u : 1u) : 0u;
-            if (!sx) r = launch_r6_rounds(ra, pace.chunk, st, e->device);
-            else {   // the chunk in pieces, a publish behind each (the chunk's last piece included: a stretch ends published)
-                r = hipSuccess;
-                for (uint32_t done = 0; done < pace.chunk && r == hipSuccess;) {
-                    const uint32_t piece = std::min<uint32_t>(stream_rounds(sx), pace.chunk - done);
-                    r = launch_r6_rounds(ra, piece, st, e->device);
-                    done += piece;
-                    if (r == hipSuccess)
-                        if (int rcp = stream_publish(e, sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rcp;
-                }
-            }
-            if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 round launch: %s", hipGetErrorString(r));
-            // (streamed: into the batch's pinned words — a copy into pageable memory may hold the host until the stream is through, and
-            // the marks are serviced while the host waits, not before)
-            HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : (void*)&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
-            if (sx) {
-                if (int rcw = stream_wait(e, sx)) return rcw;
-                std::memcpy(&hb, b->h_words.p, sizeof hb);
-            } else
-                HIPCHECK(e, hipStreamSynchronize(st));
-            if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
-            if (hb.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the %d level planes of the block resolver", R6_NP);
-            if (hb.pos <= pos) return e->fail(SWP_EHIP, "block resolver made no progress at task %u", pos);   // a round decides its first task at least
-            // The rounds of this chunk decided only a handful of tasks each: the tasks here have no plain candidates (their services run on
-            // every node that could take them) and a round ends behind the first of them. The scan resolver decides such a stretch one task
-            // after the other at ~1 us each (swp_scan.hpp); afterwards the bitmaps are rebuilt and the rounds are tried again.
-            const uint32_t used = hb.rounds - pace.rounds_seen;   // rounds that found work
-            const double recent = pace.observe(hb.pos, hb.rounds);
-            if (dbg_bits & 32) fprintf(stderr, "[swp] chunk: %u rounds, %.1f tasks each, at %u of %u | block %u compact %u csize %u clevel %u base %u maxrel %u\n", used, recent, pos, end, ra.block, ra.compact, hb.csize, hb.clevel, hb.base, hb.maxrel);
-            {
-                const uint32_t exh = hb.cut_exhausted + hb.cut_window - exh_seen, cr = hb.crounds - crounds_seen, stops = hb.reseats - stops_seen;
-                exh_seen = hb.cut_exhausted + hb.cut_window;
-                crounds_seen = hb.crounds;
-                stops_seen = hb.reseats;
-                if (cpt && cr) cpt_ever = true;
-                if (cpt_ok && !(env_cpt && atoi(env_cpt) != 0)) {
-                    if (!cpt && used >= 4 && 2 * exh >= used && recent < 0.4 * ra.block && (double)stops * 12.0 >= recent * used) cpt = true;
-                    else if (cpt && used >= 4 && cr == 0) cpt = false;
-                }
-            }
-            if (scan_ok && used >= (scan_fast ? (after_scan ? 2u : 4u) : (after_scan ? 4u : 8u)) && recent < 8.0 && end - pos >= 64) {
-              scan_again:
-                const uint32_t upto = std::min<uint64_t>(end, (uint64_t)pos + scan_len);
-                ScanArgs sa{};
-                sa.a = ra;
-                sa.j0 = pos;
-                sa.j1 = upto;
-                sa.n_svc = b->n_svc;
-                HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * N * 4));
-                HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * N * 4));
-                sa.hmat = b->d_hmat.as<uint32_t>();
-                sa.emat = b->d_emat.as<uint32_t>();
-                sa.n_sc = b->n_sc;
-                bool node_local = ra.n_rg == 0 && ra.csi_of == nullptr;   // (k_scanb: every input of a task in LDS, every effect on ONE node)
-                for (uint32_t j = pos; j < upto && node_local; ++j)
-                    if (b->rt[j].flags & RT_PORTS) node_local = false;
-                if (prof) {
-                    while (e->ev_scan.size() < (size_t)e->ev_scan_used + 2) {
-                        hipEvent_t x;
-                        HIPCHECK(e, hipEventCreate(&x));
-                        e->ev_scan.push_back(x);
-                    }
-                    HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used], st));
-                }
-                r = launch_scan(sa, st, e->device, node_local);
-                if (prof) {
-                    HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used + 1], st));
-                    e->ev_scan_used += 2;
-                }
-                e->scan_tasks_batch += upto - pos;
-                e->scan_stretches_batch += 1;
-                if (r == hipSuccess) r = launch_r6_build(ra, st);   // the rounds go on from the rows as the scan left them
-                if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan launch: %s", hipGetErrorString(r));
-                if (sx)   // (the scan kernels leave Blk6.pos at the end of their stretch)
-                    if (int rcp = stream_publish(e, sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rcp;
-                scanned += upto - pos;
-                scan_len = std::min<uint32_t>(scan_len * 2, 1u << 20);   // still no plain candidates afterwards: the next stretch is twice as long
-                pace.chunk = scan_fast ? 2 : 4;   // (round 6: sixteen rounds of ~40 us between two stretches were a sixth of the dense batch)
-                after_scan = true;
-                if (node_local && scan_fast && (upto < end || (dbg_bits & 16))) {
-                    // Most of the stretch was answered without a look (k_scanb: identical tasks had found no node — a saturated cluster's
-                    // backlog): the kernel does that at a hundred tasks a microsecond, a round of the block resolver at ten. On with it.
-                    HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : (void*)&hb, b->d_blk6.p, sizeof hb, hipMemcpyDeviceToHost, st));
-                    if (sx) {
-                        if (int rcw = stream_wait(e, sx)) return rcw;
-                        std::memcpy(&hb, b->h_words.p, sizeof hb);
-                    } else
-                        HIPCHECK(e, hipStreamSynchronize(st));
-                    const uint32_t sk = hb.scan_skipped - skipped_seen;
-                    skipped_seen = hb.scan_skipped;
-                    if (upto < end && 2 * (uint64_t)sk >= upto - pos) {
-                        pos = upto;
-                        goto scan_again;
-                    }
-                }
-                pos = upto;
-                continue;
-            }
-            after_scan = false;
-            pace.replan(recent);   // the next chunk and the next block (swp_rounds.hpp)
-            ra.block = pace.block;
-            ra.ext = ra.block < r6_block ? nullptr : r6_ext;
-            if (scan_ok) pace.chunk = std::min<uint32_t>(pace.chunk, scan_fast ? (recent < 16.0 ? 8u : recent < 64.0 ? 16u : 256u) : (recent < 16.0 ? 16u : recent < 64.0 ? 48u : 256u));   // (look again soon: rounds that hit such a stretch decide one task each)
-        }
-        if ((dbg_bits & 16) && scanned) fprintf(stderr, "[swp] k_scan decided %u tasks of [%u, %u), %u of them without a look (an identical task had found no node), the others %.2f to a barrier\n", scanned, start, end, hb.scan_skipped, (double)(scanned - hb.scan_skipped) / std::max(1u, hb.scan_batches));
-#ifdef SWP_SCAN_PROF
-        if ((dbg_bits & 16) && scanned) {
-            Ctl pc{};
-            (void)hipMemcpy(&pc, b->d_ctl.p, sizeof pc, hipMemcpyDeviceToHost);
-            const double nb_ = std::max(1u, hb.scan_batches);
-            fprintf(stderr, "[swp] k_scanb cycles per batch (wave 0; %u batches): read + evaluate %.0f, reduce + atomic %.0f, barrier %.0f, accept %.0f, apply %.0f, window work %.0f\n", hb.scan_batches,
-                    pc.cyc[0] / nb_, pc.cyc[1] / nb_, pc.cyc[2] / nb_, pc.cyc[3] / nb_, pc.cyc[4] / nb_, pc.cyc[5] / nb_);
-        }
-#endif
-        if ((dbg_bits & 16) && hb.crounds) fprintf(stderr, "[swp] %u of the %u rounds with a compact index | of the cuts at an exhausted list: %u full lists, %u lists in compact positions, %u lists of one entry\n", hb.crounds, hb.rounds, hb.dbg_cut[0], hb.dbg_cut[1], hb.dbg_cut[2]);
-        e->r6_compact_hint = cpt_ever;
-        r6_rounds += hb.rounds;
-        if (prof) HIPCHECK(e, hipEventRecord(e->ev_pool[4 * wi + 3], st));
-        ++wi;
-        if (dbg_bits & 16)
-            fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, a window that ran out %u, an exception-list task %u, an uncounted task %u\n", start, end,
-                    hb.rounds, r6_block, (double)(end - start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted);
-        if (dbg_bits & 16) {
-            const double rr_ = std::max<uint32_t>(hb.rounds, 1);
-            fprintf(stderr, "[swp] k_r6_commit shader cycles per round: prologue %.0f, matching (wave 0) %.0f (list loads %.0f, walks %.0f), the others' wait for it %.0f, apply %.0f | %.1f matcher stops at an emptied half-word per round\n",
-                    hb.cyc[0] * 64.0 / rr_, hb.cyc[1] * 64.0 / rr_, hb.cyc_load * 64.0 / rr_, hb.cyc_walk * 64.0 / rr_, hb.cyc[2] * 64.0 / rr_, hb.cyc[3] * 64.0 / rr_, hb.reseats / rr_);
-            fprintf(stderr, "[swp] ... of the list loads: waiting for a group's lists %.0f, its head records %.0f, seating %.0f (%.1f steps of the seating loop, stops included) per round\n", hb.cyc_g[0] * 64.0 / rr_,
-                    hb.cyc_g[1] * 64.0 / rr_, hb.cyc_g[2] * 64.0 / rr_, hb.cyc_g[3] / rr_);
-            fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hb.cyc_h[0] * 64.0 / rr_, hb.cyc_h[1] * 64.0 / rr_,
-                    hb.cyc_h[2] * 64.0 / rr_);
-            fprintf(stderr, "[swp] ... of the walks and behind them: inside the walk %.0f (%.1f calls), the stops %.0f, a group's epilogue (last walk to publish) %.0f per round\n", hb.cyc_s[0] * 64.0 / rr_, hb.dbg_walks / rr_,
-                    hb.cyc_s[1] * 64.0 / rr_, hb.cyc_s[2] * 64.0 / rr_);
-        }
-        return SWP_OK;
-    };
-    if (b->segs.empty()) rc = run_blocks(0, T);
+    if (run.prof) HIPCHECK(e, hipEventRecord(e->ev[1], st));
+    if ((rc = r6_run_plan(e, b, &run))) return rc;
+    if (b->segs.empty()) rc = run_stretch(e, b, run, 0, T);
     else {
         HIPCHECK(e, b->d_wf.reserve((size_t)3 * N * 4));
         for (const swp_batch::Seg& sg : b->segs) {
             if (!sg.run) {
-                if ((rc = run_blocks(sg.j0, sg.j0 + sg.n))) break;
+                if ((rc = run_stretch(e, b, run, sg.j0, sg.j0 + sg.n))) break;
                 continue;
             }
             hipError_t r = launch_waterfill(water_args_for(e, b, sg.j0, sg.n), st);
@@ -2146,60 +2190,15 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     }
     if (rc) return rc;
 
-    // explain pass: needs the number of unplaceable tasks (one small D2H, once per batch)
+    // explain pass: needs the number of unplaceable tasks (one small D2H, once per batch; streamed: the resolvers are done, every mark
+    // is there, the last range goes out)
     Ctl ctl{};
-    HIPCHECK(e, hipMemcpyAsync(sx ? b->h_words.p : (void*)&ctl, b->d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
-    if (sx) {
-        if ((rc = stream_wait(e, sx, true))) return rc;   // (the resolvers are done: every mark is there, the last range goes out)
-        std::memcpy(&ctl, b->h_words.p, sizeof ctl);
-    } else
-        HIPCHECK(e, hipStreamSynchronize(st));
-    if (prof) HIPCHECK(e, hipEventRecord(e->ev[2], st));
+    if ((rc = read_back(e, b, sx, b->d_ctl.p, &ctl, sizeof ctl, true))) return rc;
+    if (run.prof) HIPCHECK(e, hipEventRecord(e->ev[2], st));
     if (ctl.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the resolvers' level planes");
     if (ctl.ninf && (rc = run_explain(e, b, ctl.ninf))) return rc;
-    if (prof) {
-        HIPCHECK(e, hipEventRecord(e->ev[3], st));
-        HIPCHECK(e, hipEventSynchronize(e->ev[3]));
-        float a = 0, c = 0, d = 0, t = 0;
-        (void)hipEventElapsedTime(&a, e->ev[0], e->ev[1]);
-        (void)hipEventElapsedTime(&c, e->ev[1], e->ev[2]);
-        (void)hipEventElapsedTime(&d, e->ev[2], e->ev[3]);
-        (void)hipEventElapsedTime(&t, e->ev[0], e->ev[3]);
-        float scan_sum = 0, res_sum = 0;
-        for (uint32_t q = 0; q < wi; ++q) {
-            float x = 0, y = 0;
-            (void)hipEventElapsedTime(&x, e->ev_pool[4 * q + 0], e->ev_pool[4 * q + 1]);
-            (void)hipEventElapsedTime(&y, e->ev_pool[4 * q + 2], e->ev_pool[4 * q + 3]);
-            scan_sum += x;
-            res_sum += y;
-        }
-        for (uint32_t q = 0; q + 1 < e->ev_scan_used; q += 2) {   // the stretches the scan resolver took (k_scan_fill + k_scan_lists + k_scan / k_scanb each)
-            float x = 0;
-            (void)hipEventElapsedTime(&x, e->ev_scan[q], e->ev_scan[q + 1]);
-            scan_sum += x;
-        }
-        e->stats.ms_classes = a;
-        e->stats.ms_scan = scan_sum;      // Σ over windows of k_scan launch durations
-        e->stats.ms_resolve = b->segs.empty() ? res_sum : c;   // Σ of the resolver launches; with runs of identical tasks in the batch: the whole phase (k_waterfill launches + the stretches between them)
-        e->stats.ms_explain = d;
-        e->stats.ms_total = t;
-    }
-    e->stats.verify_retries += ctl.verify_retries;
-    e->stats.slow_path_tasks += ctl.slow_tasks;
-    e->stats.rebase_events += ctl.rebases;
-    e->stats.generic_tasks += ctl.generic_tasks;
-    e->stats.resolver_spins += ctl.spin_waits;
-    if (dbg_bits & 16)
-        fprintf(stderr, "[swp] resolver cycles (100MHz ticks): wait %llu prep %llu pick %llu generic %llu commit %llu blockend %llu | commits %u inf %u generic %llu\n",
-                ctl.cyc[0], ctl.cyc[1], ctl.cyc[2], ctl.cyc[3], ctl.cyc[4], ctl.cyc[5], ctl.ncommit, ctl.ninf, ctl.generic_tasks);
-    if ((dbg_bits & 16) && ctl.cyc[7])
-        fprintf(stderr, "[swp] shader clock: %llu cycles / %llu x10ns => %.0f MHz\n", ctl.cyc[6], ctl.cyc[7], (double)ctl.cyc[6] / ((double)ctl.cyc[7] * 0.01));
-    e->stats.scan_launches = e->scan_stretches_batch;
-    e->stats.scan_tasks = e->scan_tasks_batch;
-    e->stats.last_windows = wi;   // resolver stretches of this batch
-    e->stats.last_static_classes = b->n_sc;
-    e->stats.resolve_launches += (uint32_t)(2 * r6_rounds);   // k_resolve6: a propose and a commit launch per round
-    e->stats.last_resolver = 6u;   // k_resolve6
+    if (run.prof && (rc = batch_profile(e, b, run))) return rc;
+    batch_stats(e, b, run, ctl);
     b->ran = true;
     return SWP_OK;
 }
@@ -4062,7 +4061,7 @@ int r7_layout(swp_engine* e, R7Args& ma, const uint32_t* nodes_per_shard, uint32
 int r7_shard_setup(swp_engine* e, swp_batch* b, const R7Plan& plan, R6Args* out) {
     int rc = batch_begin(e, b);
     if (rc) return rc;
-    if ((rc = r6_args_for(e, b, plan.block, plan.task_rows, plan.knobs.dbg, out))) return rc;
+    if ((rc = r6_args_for(e, b, plan.block, plan.task_rows, plan.knobs, out))) return rc;
     out->tmpl = nullptr;   // a range sees only its own part of a level: its lists start at the level's first candidate
     R7Tail* tail = reinterpret_cast<R7Tail*>(out->prop + plan.block);
     HIPCHECK(e, hipMemsetAsync(tail, 0, sizeof(R7Tail), e->stream));
@@ -4316,15 +4315,7 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
         fprintf(stderr, "[swp] sharded rounds over %u engines: %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, an exception-list task %u, an uncounted task %u | set-up %.2f ms, rounds %.2f ms, explain + results %.2f ms\n", G,
                 hh.rounds, block, (double)T / std::max<uint32_t>(hh.rounds, 1), hh.cut_exhausted, hh.cut_exception, hh.cut_uncounted, ms(t_begin, t_rounds0), ms(t_rounds0, t_rounds1),
                 ms(t_rounds1, std::chrono::steady_clock::now()));
-        const double rr_ = std::max<uint32_t>(hh.rounds, 1);
-        fprintf(stderr, "[swp] k_r7_commit (shard 0) shader cycles per round: prologue + fold %.0f, matching (wave 0) %.0f (list loads %.0f, walks %.0f), apply %.0f | %.1f matcher stops at an emptied half-word per round\n",
-                hh.cyc[0] * 64.0 / rr_, hh.cyc[1] * 64.0 / rr_, hh.cyc_load * 64.0 / rr_, hh.cyc_walk * 64.0 / rr_, hh.cyc[3] * 64.0 / rr_, hh.reseats / rr_);
-        fprintf(stderr, "[swp] ... of the list loads: waiting for a group's lists %.0f, its head records %.0f, seating %.0f (%.1f steps of the seating loop, stops included) per round\n", hh.cyc_g[0] * 64.0 / rr_,
-                hh.cyc_g[1] * 64.0 / rr_, hh.cyc_g[2] * 64.0 / rr_, hh.cyc_g[3] / rr_);
-        fprintf(stderr, "[swp] ... of the head records: up to the first use of the record / template id %.0f, flags and cursor from LDS %.0f, the run path %.0f per round\n", hh.cyc_h[0] * 64.0 / rr_, hh.cyc_h[1] * 64.0 / rr_,
-                hh.cyc_h[2] * 64.0 / rr_);
-        fprintf(stderr, "[swp] ... of the walks and behind them: inside the walk %.0f (%.1f calls), the stops %.0f, a group's epilogue (last walk to publish) %.0f per round\n", hh.cyc_s[0] * 64.0 / rr_, hh.dbg_walks / rr_,
-                hh.cyc_s[1] * 64.0 / rr_, hh.cyc_s[2] * 64.0 / rr_);
+        r6_report(hh, true);
     }
     cleanup();
     return SWP_OK;

@@ -1,7 +1,9 @@
-// swp_rounds.hpp — what the three drivers of the block resolver's rounds decide on the host, written once: the knobs, the row mode, the
-// block that fits the commit kernel's LDS, and the pace (how many rounds to enqueue before the next look, and with which block).
-// batch_run_impl (one engine), swp_shard_run (G engines in one process) and swp_shard_run_rank (one engine per rank) use it; between
-// ranks every rank MUST derive the same chunk and the same block from the same gathered words, or their collectives stop lining up.
+// swp_rounds.hpp — every host rule of the block resolver's rounds, written once: the knobs, the row mode, runs and window, the block that
+// fits the commit kernel's LDS, the pace (how many rounds to enqueue before the next look, and with which block), and what the single
+// engine's driver adds to it: the compact switch, the hand-over to the scan resolver, and the two together as one stretch's rules
+// (RoundRules). batch_run_impl (one engine) uses all of it, swp_shard_run (G engines in one process) and swp_shard_run_rank (one engine
+// per rank) the knobs, the row mode, the fit and the pace; between ranks every rank MUST derive the same chunk and the same block from
+// the same gathered words, or their collectives stop lining up. The drivers keep the mechanics (launches, read-backs, events, reports).
 // No HIP and no engine types in here: tests/emu/emu_rounds.cpp compiles this header alone with g++ (tests/test_rounds_cpu.py).
 #pragma once
 #include <algorithm>
@@ -17,7 +19,16 @@ struct R6Knobs {
     bool block_forced = false;   // SWP_R6_BLOCK is set: the block stays what it says (as far as the LDS allows), whatever the pace
     uint32_t block_cap = 0;      // tasks per round at most: the knob or default_cap, within [1, block_max]
     int task_rows = -1;          // SWP_R6_TASKROWS: -1 unset, else 0 / 1
+    int runs = -1;               // SWP_R6_RUNS: -1 unset (the batch decides: r6_shape), else 0 / 1 (tests, A/B runs)
+    int compact = -1;            // SWP_R6_COMPACT: -1 unset (the rounds' symptom decides: CompactSwitch), 0 never, 1 from the first round on
+    bool compact_fused = true;   // SWP_R6_COMPACT_FUSED=0: the index of the next round by a launch of its own, not at the end of k_r6_commit_c
+    bool scan = true;            // SWP_SCAN=0: never hand a stretch to the scan resolver
+    bool twins = true;           // SWP_R6_TWINS=0: every list starts at its level's first candidate
 };
+inline int r6_knob01(const char* name) {   // -1 unset, else 0 / 1
+    const char* env = getenv(name);
+    return env ? (atoi(env) != 0 ? 1 : 0) : -1;
+}
 inline R6Knobs r6_knobs(uint32_t block_max, uint32_t default_cap) {
     R6Knobs k;
     const char* env_dbg = getenv("SWP_DBG");
@@ -25,8 +36,12 @@ inline R6Knobs r6_knobs(uint32_t block_max, uint32_t default_cap) {
     const char* env_blk = getenv("SWP_R6_BLOCK");
     k.block_forced = env_blk != nullptr;
     k.block_cap = std::min<uint32_t>(block_max, std::max<uint32_t>(1u, env_blk ? (uint32_t)atoi(env_blk) : default_cap));
-    const char* env_tr = getenv("SWP_R6_TASKROWS");
-    if (env_tr) k.task_rows = atoi(env_tr) != 0 ? 1 : 0;
+    k.task_rows = r6_knob01("SWP_R6_TASKROWS");
+    k.runs = r6_knob01("SWP_R6_RUNS");
+    k.compact = r6_knob01("SWP_R6_COMPACT");
+    k.compact_fused = r6_knob01("SWP_R6_COMPACT_FUSED") != 0;
+    k.scan = r6_knob01("SWP_SCAN") != 0;
+    k.twins = r6_knob01("SWP_R6_TWINS") != 0;
     return k;
 }
 
@@ -83,6 +98,114 @@ struct RoundPace {
         const double recent = observe(pos_now, rounds_now);
         replan(recent);
         return recent;
+    }
+};
+
+// A batch that is mostly RUNS of identical tasks (service-major order) keeps whole proposals in LDS and the blocks they allow: the
+// runs-by-rank path (runs of >= 8) takes a run's picks from ONE task's window, and with windows of 16 in blocks of 1 408 service-major
+// cfg3 — every task in a run of 100 — took 327 rounds and 12.6 ms where the parent took 288 and 10.2 (profiles/late_window.json,
+// "major_windows_of_16"). Measured at the two ends only — no task in such a run (the headline), every task in one; the line between
+// them is drawn at half the batch's tasks, counted once when the batch is built. SWP_R6_RUNS forces either; SWP_R6_BLOCK the block.
+struct R6Shape { bool runs; uint32_t win, cap; };   // win: a proposal's entries in the commit kernel's LDS (0: late windows of 16); cap: tasks per round at most, before the fit
+inline R6Shape r6_shape(const R6Knobs& k, uint32_t tasks_in_runs, uint32_t T) {
+    const bool runs = k.runs >= 0 ? k.runs != 0 : 2u * (uint64_t)tasks_in_runs > T;
+    return R6Shape{runs, runs ? 32u : 0u, (runs && !k.block_forced) ? std::min<uint32_t>(k.block_cap, 768u) : k.block_cap};
+}
+
+// The words of the control block the rules below read after a chunk of rounds or behind a scan stretch, all running totals: decided up
+// to pos; rounds that found work; rounds cut by an exhausted list or a window that ran out; rounds that had a compact index; matcher
+// stops at an emptied half-word; tasks the batched scan answered without a look.
+struct R6Words { uint32_t pos, rounds, cuts, crounds, reseats, scan_skipped; };
+
+// The compact index (swp_resolve6.hpp, R6Args.compact): one more small launch per round, worth it when the level the tasks aim at is a
+// sparse set of nodes (re-placements after a drain): the matcher then stops at an emptied half-word every few tasks and the rounds are
+// cut by exhausted lists after a fraction of their block. Switched on by that symptom (a stop per <= 12 decided tasks; ordinary
+// batches have one per 30-40), off again when the kernel found no such level in a whole chunk. `ever` (some chunk had rounds with an
+// index) is the next batch's hint: a churn round's batch ENDS on tasks that aim at a level every node has, and a hint that said "the
+// last chunk had one" began every batch with sixteen rounds without the index. (Starting with the previous batch's small BLOCK as well
+// was measured and lost: device 3.39 -> 3.62 ms a round, same box, three runs each.)
+struct CompactSwitch {
+    bool ok, pinned, fused, on, ever = false;   // ok: may be built at all; pinned: SWP_R6_COMPACT non-zero, on whatever the rounds say
+    uint32_t cuts_seen = 0, crounds_seen = 0, stops_seen = 0;
+    // allowed: the caller's LDS and volume test; hint: the engine's, from the batch before
+    CompactSwitch(bool allowed, const R6Knobs& k, bool hint) : ok(allowed && k.compact != 0), pinned(k.compact > 0), fused(k.compact_fused), on(ok && (pinned || hint)) {}
+    uint32_t compact() const { return on ? (fused ? 2u : 1u) : 0u; }   // R6Args.compact of the next chunk
+    // after a chunk: `used` rounds found work and decided `recent` tasks each, with blocks of `block`
+    void feed(uint32_t used, double recent, uint32_t block, const R6Words& w) {
+        const uint32_t exh = w.cuts - cuts_seen, cr = w.crounds - crounds_seen, stops = w.reseats - stops_seen;
+        cuts_seen = w.cuts;
+        crounds_seen = w.crounds;
+        stops_seen = w.reseats;
+        if (on && cr) ever = true;
+        if (!ok || pinned) return;
+        if (!on && used >= 4 && 2 * exh >= used && recent < 0.4 * block && (double)stops * 12.0 >= recent * used) on = true;
+        else if (on && used >= 4 && cr == 0) on = false;
+    }
+};
+
+// Rounds that decide only a handful of tasks each: the tasks there have no plain candidates (their services run on every node that
+// could take them) and a round ends behind the first of them. The scan resolver decides such a stretch one task after the other
+// (swp_scan.hpp); afterwards the bitmaps are rebuilt and the rounds are tried again. Its batched instance (k_scanb) decides ~4 tasks a
+// barrier and answers an unplaceable task's twins without a look: where it can run (`fast`), a stretch goes to it after four poor
+// rounds and two probing rounds follow it; the one-task-a-barrier instance (~1 us a task) has to be worth more: eight poor rounds,
+// four probes. (Sixteen rounds of ~40 us between two stretches were a sixth of the dense batch.)
+struct ScanHandover {
+    bool ok, fast;
+    uint32_t len = 2048;       // tasks of the next stretch: still no plain candidates afterwards, and it is twice as long
+    bool after_scan = false;   // the rounds since the last stretch: a few of them say whether the tasks still have no plain candidates
+    uint32_t skipped_seen = 0, scanned = 0;
+    ScanHandover(bool ok_, bool fast_) : ok(ok_), fast(ok_ && fast_) {}
+    bool due(uint32_t used, double recent, uint32_t left) const { return ok && used >= (fast ? (after_scan ? 2u : 4u) : (after_scan ? 4u : 8u)) && recent < 8.0 && left >= 64; }
+    uint32_t upto(uint32_t pos, uint32_t end) const { return (uint32_t)std::min<uint64_t>(end, (uint64_t)pos + len); }
+    uint32_t took(uint32_t pos, uint32_t upto) {   // the stretch [pos, upto) was enqueued -> the probing rounds behind it
+        scanned += upto - pos;
+        len = std::min<uint32_t>(len * 2, 1u << 20);
+        after_scan = true;
+        return fast ? 2u : 4u;
+    }
+    // the words are read behind a node-local stretch of the batched instance: for `again`, and at the end for the driver's report only
+    bool looks(bool node_local, uint32_t upto, uint32_t end, bool report) const { return node_local && fast && (upto < end || report); }
+    // Most of the stretch was answered without a look (identical tasks had found no node — a saturated cluster's backlog): the kernel
+    // does that at a hundred tasks a microsecond, a round of the block resolver at ten. Another stretch directly behind this one.
+    bool again(uint32_t pos, uint32_t upto, uint32_t end, uint32_t scan_skipped) {
+        const uint32_t sk = scan_skipped - skipped_seen;
+        skipped_seen = scan_skipped;
+        return upto < end && 2 * (uint64_t)sk >= upto - pos;
+    }
+    uint32_t cap_chunk(uint32_t chunk, double recent) const {   // look again soon: rounds that hit such a stretch decide one task each
+        return !ok ? chunk : std::min<uint32_t>(chunk, fast ? (recent < 16.0 ? 8u : recent < 64.0 ? 16u : 256u) : (recent < 16.0 ? 16u : recent < 64.0 ? 48u : 256u));
+    }
+};
+
+// One stretch of the single engine's rounds: pace, switch and hand-over together. The driver enqueues pace.chunk rounds with pace.block,
+// cpt.compact() and ext(), reads the words and asks after_rounds; where that says so it enqueues the scan stretch [pace.pos, scan_upto()),
+// reads the words again where scan.looks says so, and asks after_scan — until pace.pos reaches pace.end.
+struct RoundRules {
+    RoundPace pace;
+    CompactSwitch cpt;
+    ScanHandover scan;
+    bool ext_ok;   // lists beyond a proposal's 32 entries: not for a batch of runs, whose windows hold a whole proposal ...
+    bool ext() const { return ext_ok && pace.block >= pace.largest; }   // ... nor for rounds whose block the pace has shrunk
+    // The words behind a chunk. true: a stretch goes to the scan resolver, and the rounds behind it keep block and ext (no replan);
+    // false: the next chunk and the next block are planned. `used` is taken before the pace moves on.
+    bool after_rounds(const R6Words& w, uint32_t* used, double* recent) {
+        const uint32_t block = pace.block;
+        *used = w.rounds - pace.rounds_seen;
+        *recent = pace.observe(w.pos, w.rounds);
+        cpt.feed(*used, *recent, block, w);
+        if (scan.due(*used, *recent, pace.end - pace.pos)) return true;
+        scan.after_scan = false;
+        pace.replan(*recent);
+        pace.chunk = scan.cap_chunk(pace.chunk, *recent);
+        return false;
+    }
+    uint32_t scan_upto() const { return scan.upto(pace.pos, pace.end); }
+    // The stretch [pace.pos, upto) was enqueued; `looked`: the words behind it, or null where scan.looks said no. true: another one.
+    bool after_scan(uint32_t upto, const R6Words* looked) {
+        pace.chunk = scan.took(pace.pos, upto);
+        const bool again = looked && scan.again(pace.pos, upto, pace.end, looked->scan_skipped);
+        pace.pos = upto;
+        return again;
     }
 };
 
