@@ -2036,8 +2036,8 @@ void stretch_report(swp_batch* b, const R6Run& run, const R6Stretch& s) {
     }
 #endif
     if (hb.crounds) fprintf(stderr, "[swp] %u of the %u rounds with a compact index | of the cuts at an exhausted list: %u full lists, %u lists in compact positions, %u lists of one entry\n", hb.crounds, hb.rounds, hb.dbg_cut[0], hb.dbg_cut[1], hb.dbg_cut[2]);
-    fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, a window that ran out %u, an exception-list task %u, an uncounted task %u\n", s.start, s.end,
-            hb.rounds, run.block, (double)(s.end - s.start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted);
+    fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, a window that ran out %u, an exception-list task %u, an uncounted task %u | proposals with a second section %u\n", s.start, s.end,
+            hb.rounds, run.block, (double)(s.end - s.start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted, hb.dbg_lv2);
     r6_report(hb, false);
 }
 
@@ -2087,6 +2087,7 @@ int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_
         s.ra.block = pace.block;
         s.ra.compact = s.rules.cpt.compact();
         s.ra.ext = s.rules.ext() ? b->d_ext.as<R6PropExt>() : nullptr;
+        s.ra.levels2 = r6_levels2(run.knobs, s.ra.ext != nullptr, s.ra.n_words, R6_LIST) ? 1u : 0u;
         if (int rc = launch_chunk(e, b, run.sx, s.ra, pace.chunk)) return rc;
         if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
         if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");

@@ -17,7 +17,8 @@
 //                  the word's minimum level); one reduction gives the task's minimum level, the words whose own minimum equals it
 //                  hold exactly its candidates. The first 2 * R6_CAND non-empty half-words go into the task's proposal, with the
 //                  best node of the service's exception list by the full key when there is no plain candidate; up to R6_LIST in all
-//                  with the side record R6Args.ext.
+//                  with the side record R6Args.ext. A complete list goes on, where the host says so (R6Args.levels2), with a SECOND SECTION:
+//                  the task's candidates one level up that lie in front of the first section ("the second section" in r6_propose_t).
 //   k_r6_commit    one workgroup of 1 024. LDS holds a window of every task's list (entry-major): its first R6_WIN entries that are live
 //                  when its group is staged — groups 0 and 1 by the prologue, group g by its applying wave two groups ahead of the
 //                  matcher (r6_commit_t). Wave 0 walks the block in task order, 64 tasks at a time: a lane seats the first two half-words of its list that still have a candidate
@@ -33,7 +34,9 @@
 //                  where plain half-words hold three of the few emptied nodes — the others plain half-words behind them
 //                  (R6Args.compact, the _c instances of the two kernels).
 // The exactness argument is the list rule: inside a batch levels only grow and feasibility only shrinks, and a list
-// holds ALL plain candidates of the task's minimum level in node order up to its last half-word.
+// holds ALL plain candidates of the task's minimum level in node order up to its last half-word. Half-words ascend PER SECTION: a list
+// is in preference order, and the commit kernel takes its entries as opaque (half-word, bits) pairs in that order — the window staging,
+// the cursor loops, the seating step, the runs-by-rank path and wv::match_seq64 compare half-words for equality only, never for order.
 //
 // Written against swp_wave.hpp only, so tests/emu runs the same source on CPU fibers (tests/test_emu_resolve6.py).
 #pragma once
@@ -52,6 +55,9 @@ namespace swpdev {
 #define R6_SEAT 2                 // list entries a seating step of the matcher looks at (4 measured no better: fewer steps, each longer)
 #ifndef R6_SEAT_AHEAD
 #define R6_SEAT_AHEAD 1          // the matcher requests the entries at a lane's cursor when the cursor moves, not when it stops there (0: at the stop — A/B builds, tests/emu)
+#endif
+#ifndef R6_LEVELS2
+#define R6_LEVELS2 1             // the propose kernels know the second list section (R6Args.levels2); 0: compiled out (A/B builds, tests/emu)
 #endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #define R6_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)   // the instruction scheduler moves nothing across this point (not a memory fence, no instruction)
@@ -89,12 +95,15 @@ struct Blk6 {   // control block, global memory
     u32 cyc_s[3];          // dbg: cyc_walk split (and what follows it) — inside wv::match_seq64, the stops (a walk's return to the next walk's entry, or to
                            // the cut at an exhausted list), a group's epilogue (its last walk's end to the publish of its picks)
     u32 dbg_walks;         // dbg: calls of wv::match_seq64
+    u32 dbg_lv2;           // dbg: proposals that carried a second section (R6Args.levels2), counted by the propose kernel
 };
-static_assert(sizeof(Blk6) == 148, "Blk6 layout");
+static_assert(sizeof(Blk6) == 152, "Blk6 layout");
 
 struct R6Prop {   // one task's proposal: the shard protocol's record (include/swp.h swp_proposal) with more candidates, as 32-node half-words
     u32 level, n_cand;       // minimum level among the plain candidates (R6_NONE: there is none); half-words listed | bit 31: there are more
-    unsigned short hw[2 * R6_CAND];   // half-word index (node = 32 * hw + bit), ascending: the first 2 * R6_CAND NON-EMPTY half-words of the level — 16 bits
+                             // (R6Args.levels2: the entries of a second section count; `level` stays the first section's; bit 31: the room cut the second)
+    unsigned short hw[2 * R6_CAND];   // half-word index (node = 32 * hw + bit), ascending PER SECTION (the list is in preference order: the level's half-words, then —
+                                      // R6Args.levels2 — half-words of the next level that all lie in front of them): the first 2 * R6_CAND NON-EMPTY half-words — 16 bits
                                       // (round 6: node sets end at 2^21 nodes): a record is 224 bytes instead of 288, to write, to stage, to fold and to all-gather
     u32 hb[2 * R6_CAND];     // the level's survivors inside each
     u64 exc_hi, exc_lo;      // best node of the service's exception list by nodeLess' key, KEY_NONE: none
@@ -185,6 +194,8 @@ struct R6Args {
     u32 no_runs;             // != 0: the batch has no run of >= 8 consecutive identical tasks (counted when it is built): the matcher leaves the
                              // runs-by-rank path and the descriptor ids it reads alone (its entry found nothing in every group of the headline:
                              // 4 650 of a round's 160 k cycles)
+    u32 levels2;             // != 0: a complete list goes on with a SECOND SECTION, the task's candidates one level up that lie in front of the first
+                             // section (r6_propose_t, "the second section"); 0: lists of one level. Honoured by the instances without a compact index
 };
 struct R7Args;   // swp_resolve7.hpp: what a shard's commit kernel knows of the other shards
 #define R7_FOLDS_IN_FLIGHT 4u   // waves that fold at the same time (the R7 staging below); SWP_DBG bits 8-11 override it for A/B runs (tools/gpu_r5_foldwin.sh)
@@ -233,6 +244,13 @@ WV_DEV u32 r7_addr(const R7Args* m, u32 shard, u32 node);
 WV_DEV u32 r7_local(const R7Args* m, u32 addr, u32 my, bool* here);
 WV_DEV u32 r7_take_trailers(const R6Args& a, const R7Args* m, u32 my, u32 round);
 WV_DEV void r7_leave_trailer(const R6Args& a, u32 my, u32 round, u32 set, u32 node, const u32* att, u32 n);
+
+// a counter many workgroups add to (reports under R6Args.dbg only). On the CPU fibers one thread runs at a time: a plain add.
+#if defined(__HIPCC__)
+WV_DEV void r6_count32(u32* p) { __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#else
+inline void r6_count32(u32* p) { *p += 1u; }
+#endif
 
 WV_DEV u64 r6_wave_min64(u64 v) {
     const u32 hi = (u32)(v >> 32), lo = (u32)v;
@@ -618,12 +636,38 @@ template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(con
     const u32 lmax = ext ? (u32)R6_LIST : 2u * R6_CAND;
     u32 cnt = 0, more = 0;
     u32 skip = twins, last_hw = 0, last_hb = 0;   // candidates still to pass over; the last non-empty half-word passed over
+    u32 h0 = R6_NONE;   // the half-word of the level's first candidate, the twins' share included (the second section ends in front of its word)
+    // the non-empty halves (lo, hi) of the lanes' words of chunk k go to the list behind its `cnt` entries, in lane order
+    auto put = [&](u32 k, u32 lo, u32 hi, u64 b_lo, u64 b_hi) {
+        const u32 at_lo = cnt + wv::mbcnt(b_lo) + wv::mbcnt(b_hi), at_hi = at_lo + (lo != 0 ? 1u : 0u);
+        if (lo && at_lo < 2 * R6_CAND) {
+            out->hw[at_lo] = (unsigned short)(hw_off + 2 * (k * 64 + lane));
+            out->hb[at_lo] = lo;
+        } else if (lo && at_lo < lmax) {
+            ext->hw[at_lo - 2 * R6_CAND] = (unsigned short)(hw_off + 2 * (k * 64 + lane));
+            ext->hb[at_lo - 2 * R6_CAND] = lo;
+        }
+        if (hi && at_hi < 2 * R6_CAND) {
+            out->hw[at_hi] = (unsigned short)(hw_off + 2 * (k * 64 + lane) + 1);
+            out->hb[at_hi] = hi;
+        } else if (hi && at_hi < lmax) {
+            ext->hw[at_hi - 2 * R6_CAND] = (unsigned short)(hw_off + 2 * (k * 64 + lane) + 1);
+            ext->hb[at_hi - 2 * R6_CAND] = hi;
+        }
+        const u32 total = cnt + (u32)wv::popc64(b_lo) + (u32)wv::popc64(b_hi);
+        if (total > lmax) more = 1;
+        cnt = min(total, lmax);
+    };
     if (level != R6_NONE)
         for (u32 k = 0; k < (nw + 63u) / 64u && !more; ++k) {   // (the chunks beyond the row hold nothing)
             const u64 m = cmode ? (k * 64 + lane < VW ? V[k * 64 + lane] : 0ull) : (R[k * 64 + lane] == gmin ? A[k * 64 + lane] : 0ull);   // the words whose own minimum is the task's
             u32 lo = (u32)m, hi = (u32)(m >> 32);
             u64 b_lo = wv::ballot(lo != 0), b_hi = wv::ballot(hi != 0);
             if (!(b_lo | b_hi)) continue;
+            if (R6_LEVELS2 && !CPT && h0 == R6_NONE) {
+                const u32 fl = (u32)wv::ffs64(b_lo | b_hi);
+                h0 = 2 * (k * 64 + fl) + (((b_lo >> fl) & 1ull) ? 0u : 1u);
+            }
             if (skip) {
                 // candidates in front of a lane's word: the popcounts (<= 64: seven bits) summed over the lower lanes plane by plane
                 const u32 pl = (u32)wv::popc64((u64)lo), pc = pl + (u32)wv::popc64((u64)hi);
@@ -657,25 +701,39 @@ template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(con
                 b_hi = wv::ballot(hi != 0);
                 if (!(b_lo | b_hi)) continue;
             }
-            const u32 at_lo = cnt + wv::mbcnt(b_lo) + wv::mbcnt(b_hi), at_hi = at_lo + (lo != 0 ? 1u : 0u);
-            if (lo && at_lo < 2 * R6_CAND) {
-                out->hw[at_lo] = (unsigned short)(hw_off + 2 * (k * 64 + lane));
-                out->hb[at_lo] = lo;
-            } else if (lo && at_lo < lmax) {
-                ext->hw[at_lo - 2 * R6_CAND] = (unsigned short)(hw_off + 2 * (k * 64 + lane));
-                ext->hb[at_lo - 2 * R6_CAND] = lo;
-            }
-            if (hi && at_hi < 2 * R6_CAND) {
-                out->hw[at_hi] = (unsigned short)(hw_off + 2 * (k * 64 + lane) + 1);
-                out->hb[at_hi] = hi;
-            } else if (hi && at_hi < lmax) {
-                ext->hw[at_hi - 2 * R6_CAND] = (unsigned short)(hw_off + 2 * (k * 64 + lane) + 1);
-                ext->hb[at_hi - 2 * R6_CAND] = hi;
-            }
-            const u32 total = cnt + (u32)wv::popc64(b_lo) + (u32)wv::popc64(b_hi);
-            if (total > lmax) more = 1;
-            cnt = min(total, lmax);
+            put(k, lo, hi, b_lo, b_hi);
         }
+    // ---- the second section (R6Args.levels2): where a lap over the node set ends, one class of tasks after the other finds every node
+    // of its minimum level L taken; what such a task wants then is the first node of level L + 1 that passes its filters, and at propose
+    // time that is known. A COMPLETE level-L listing (not cut by the list's length, the twins' share below the level's candidates) of a
+    // task without cluster mounts goes on with the first non-empty half-words, in node order, of the task's plain candidates on level
+    // EXACTLY L + 1 that lie in words in front of h0's — the half-word of the level's first candidate, the twins' share included — as
+    // far as the list has room (bit 31 of n_cand: the room cut the section). R6Prop.level stays L. Exact, because
+    //   * inside a block levels only grow and feasibility only shrinks: no candidate on a level <= L ever appears, so once the first
+    //     section is dead the task's candidates on L + 1 are nodes that were on L + 1 at propose time and nodes the block moved up from L;
+    //   * a node moved up that passes the task's filters was one of its level-L candidates: it lies in a half-word >= h0, behind every
+    //     entry of the section — and so does every L + 1 node the section left out. A live listed entry beats them all;
+    //   * a listed node whose TK bit is clear is as the propose saw it: no task of the block was placed on it, X of the service moves on
+    //     taken nodes only (volumes are the one cluster-wide state: tasks with mounts get no section); one a crossing task took is struck
+    //     like any other (its TK bit stays set, it moved to L + 2);
+    //   * L + 1 exactly: on a higher level a node moved up to L + 1 would win whatever its index. Beyond Blk6.maxrel there is nothing to list;
+    //   * a section that is empty or runs dry cuts the block, as a list of one level does. A cut is always allowed.
+    // Nothing is loaded: the first pass left every word's candidates on the WORD's minimum level in A and that level in R, and a word
+    // in front of h0's has no candidate on L — its minimum is L + 1 or it holds none of that level. (The low half of h0's own word, when h0
+    // is a high half, is left out with everything behind it: its L + 1 candidates are not in A.) Entries are (half-word, bits) pairs
+    // to the commit kernel, which walks them in list order: the two sections never share a half-word, their bit sets are disjoint.
+    u32 first_len = cnt;
+    if (R6_LEVELS2 && !CPT && a.levels2 && level != R6_NONE && !more && cnt != 0 && cnt < lmax && ck == R6_NONE && gmin < maxrel && h0 != R6_NONE) {
+        const u32 w_end = h0 >> 1;   // (0: the level's first candidate sits in word 0, no section)
+        for (u32 k = 0; k * 64 < w_end && !more; ++k) {
+            const u32 idx = k * 64 + lane;
+            const u64 m = (idx < w_end && R[idx] == gmin + 1u) ? A[idx] : 0ull;
+            const u32 lo = (u32)m, hi = (u32)(m >> 32);
+            const u64 b_lo = wv::ballot(lo != 0), b_hi = wv::ballot(hi != 0);
+            if (b_lo | b_hi) put(k, lo, hi, b_lo, b_hi);
+        }
+        if ((a.dbg & 16u) && cnt > first_len && lane == 0) r6_count32(&a.blk->dbg_lv2);
+    }
     // no plain candidate: the service's exception list by the full key (scheduler.go:708-735), lanes stride over the entries
     u64 bhi = KEY_NONE, blo = KEY_NONE;
     u32 be = 0;

@@ -24,6 +24,7 @@ struct R6Knobs {
     bool compact_fused = true;   // SWP_R6_COMPACT_FUSED=0: the index of the next round by a launch of its own, not at the end of k_r6_commit_c
     bool scan = true;            // SWP_SCAN=0: never hand a stretch to the scan resolver
     bool twins = true;           // SWP_R6_TWINS=0: every list starts at its level's first candidate
+    int levels = -1;             // SWP_R6_LEVELS: -1 unset and 1: lists over two levels where the rule allows them (r6_levels2), 0: never
 };
 inline int r6_knob01(const char* name) {   // -1 unset, else 0 / 1
     const char* env = getenv(name);
@@ -42,6 +43,7 @@ inline R6Knobs r6_knobs(uint32_t block_max, uint32_t default_cap) {
     k.compact_fused = r6_knob01("SWP_R6_COMPACT_FUSED") != 0;
     k.scan = r6_knob01("SWP_SCAN") != 0;
     k.twins = r6_knob01("SWP_R6_TWINS") != 0;
+    k.levels = r6_knob01("SWP_R6_LEVELS");
     return k;
 }
 
@@ -111,6 +113,14 @@ inline R6Shape r6_shape(const R6Knobs& k, uint32_t tasks_in_runs, uint32_t T) {
     const bool runs = k.runs >= 0 ? k.runs != 0 : 2u * (uint64_t)tasks_in_runs > T;
     return R6Shape{runs, runs ? 32u : 0u, (runs && !k.block_forced) ? std::min<uint32_t>(k.block_cap, 768u) : k.block_cap};
 }
+
+// Lists over two levels (swp_resolve6.hpp, R6Args.levels2): a complete list goes on with the task's candidates one level up that lie in
+// front of it, so that the tasks which find their level used up where a lap over the node set ends are decided in the same round instead
+// of cutting it (the headline: 126 rounds -> 73). It uses the room of the long lists, so it is on where they are (`ext_on`,
+// RoundRules::ext(): not for a batch of runs, not for rounds whose block the pace has shrunk — the churn rounds, the compact index),
+// and only on node sets with more half-words than a list holds (`list` = R6_LIST): on a smaller one a complete list names the whole
+// level and what is in front of it is a handful of words. SWP_R6_LEVELS=0 switches it off; 1 is the default spelled out.
+inline bool r6_levels2(const R6Knobs& k, bool ext_on, uint32_t n_words, uint32_t list) { return k.levels != 0 && ext_on && 2u * (uint64_t)n_words > list; }
 
 // The words of the control block the rules below read after a chunk of rounds or behind a scan stretch, all running totals: decided up
 // to pos; rounds that found work; rounds cut by an exhausted list or a window that ran out; rounds that had a compact index; matcher
