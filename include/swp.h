@@ -653,7 +653,9 @@ typedef struct {
     uint32_t propose_launches, propose_tasks;   /* launches and Σ tasks proposed (a task cut off a block is proposed again) */
     uint32_t waterfill_tasks;   /* tasks placed as runs of identical tasks (k_waterfill), since swp_create */
     uint32_t scan_tasks;        /* last batch: tasks the scan resolver decided (k_scan / k_scanb: stretches without plain candidates); scan_launches
-                                   counts those stretches and ms_scan their time (SWP_CFG_PROFILE) */
+                                   counts those stretches and ms_scan their time (SWP_CFG_PROFILE). A stretch that went through the compact
+                                   instance — a cluster of more than 4 096 nodes, the union of the stretch's class rows at most that — is
+                                   counted like any other, in both; a probe that refused a stretch is counted in neither */
 } swp_stats_t;
 
 int swp_create(const swp_config*, swp_engine** out);

@@ -444,6 +444,7 @@ struct swp_batch {
     PinBuf h_up;
     DevBuf d_rt, d_out, d_hist, d_X, d_list_node, d_list_svc, d_list_fail, d_list_node0, d_list_svc0, d_list_fail0, d_list_off;
     DevBuf d_hmat, d_emat;   // the scan resolver's (service, node) matrices, allocated when a stretch first goes to it
+    DevBuf d_scanc;          // its compact instance's probe: node count, class-row marks, union, prefix sums, map (scan_compact_bufs)
     DevBuf d_prow, d_pnode, d_portmap, d_pset_off, d_pset_ids;
     DevBuf d_con_off, d_cons, d_plat_off, d_plats, d_plug_off, d_plug_req, d_triples;
     DevBuf d_con, d_plat, d_plug, d_sc, d_log_node, d_log_task, d_log_prev, d_last, d_inf_task, d_inf_pos, d_ctl;
@@ -1967,30 +1968,65 @@ int launch_chunk(swp_engine* e, swp_batch* b, StreamRun* sx, const R6Args& ra, u
     return SWP_OK;
 }
 
+// The compact instance's buffers, one allocation: [0] the union's node count, then the class-row marks, the union, its prefix sums, the map.
+int scan_compact_bufs(swp_engine* e, swp_batch* b, ScanArgs* sa) {
+    const size_t Wn = n_words_of(e->n_nodes), o_used = 64, o_u = (o_used + (size_t)b->n_sc * 4 + 63) & ~(size_t)63, o_pre = o_u + Wn * 8, o_map = (o_pre + Wn * 4 + 63) & ~(size_t)63;
+    HIPCHECK(e, b->d_scanc.reserve(o_map + (size_t)scan_max_nodes() * 4));
+    char* base = b->d_scanc.as<char>();
+    sa->cnc = reinterpret_cast<uint32_t*>(base);
+    sa->cused = reinterpret_cast<uint32_t*>(base + o_used);
+    sa->cu = reinterpret_cast<u64*>(base + o_u);
+    sa->cpre = reinterpret_cast<uint32_t*>(base + o_pre);
+    sa->cmap = reinterpret_cast<uint32_t*>(base + o_map);
+    return SWP_OK;
+}
+
+// The probe of the compact instance: the node count of the union of the class rows the tasks [pos, upto) name, read back as the words
+// behind a chunk are (streamed: through the pinned words). Union, prefix sums and map stay on the device for the stretch that may follow.
+int scan_probe(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t pos, uint32_t upto, uint32_t* union_nodes) {
+    ScanArgs sa{};
+    sa.a = ra;
+    sa.j0 = pos;
+    sa.j1 = upto;
+    sa.n_svc = b->n_svc;
+    sa.n_sc = b->n_sc;
+    if (int rc = scan_compact_bufs(e, b, &sa)) return rc;
+    const hipError_t r = launch_scan_probe(sa, e->stream);
+    if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan_union launch: %s", hipGetErrorString(r));
+    return read_back(e, b, run.sx, sa.cnc, union_nodes, sizeof *union_nodes);
+}
+
 // The tasks [pos, upto) to the scan resolver, one after the other (swp_scan.hpp); behind it the bitmaps rebuilt — the rounds go on from
 // the rows as the scan left them — and, streamed, a publish (the scan kernels leave Blk6.pos at the end of their stretch).
 // *node_local: k_scanb could take it (every input of a task in LDS, every effect on ONE node).
-int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t pos, uint32_t upto, bool* node_local) {
+// union_nodes != 0: through the compact instance, over the union the probe of [pos, upto) left in the batch's buffers (never node_local:
+// the batched instance has no compact form).
+int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t pos, uint32_t upto, bool* node_local, uint32_t union_nodes = 0) {
     hipStream_t st = e->stream;
     ScanArgs sa{};
     sa.a = ra;
     sa.j0 = pos;
     sa.j1 = upto;
     sa.n_svc = b->n_svc;
-    HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * e->n_nodes * 4));
-    HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * e->n_nodes * 4));
+    const size_t cols = union_nodes ? union_nodes : e->n_nodes;
+    HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * cols * 4));
+    HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * cols * 4));
     sa.hmat = b->d_hmat.as<uint32_t>();
     sa.emat = b->d_emat.as<uint32_t>();
     sa.n_sc = b->n_sc;
-    bool local = ra.n_rg == 0 && ra.csi_of == nullptr;
+    bool local = ra.n_rg == 0 && ra.csi_of == nullptr && !union_nodes;
     for (uint32_t j = pos; j < upto && local; ++j)
         if (b->rt[j].flags & RT_PORTS) local = false;
     *node_local = local;
+    if (union_nodes) {
+        if (int rc = scan_compact_bufs(e, b, &sa)) return rc;
+        sa.n_c = union_nodes;
+    }
     if (run.prof) {
         if (int rc = grow_events(e, e->ev_scan, (size_t)e->ev_scan_used + 2)) return rc;
         HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used], st));
     }
-    hipError_t r = launch_scan(sa, st, e->device, local);
+    hipError_t r = union_nodes ? launch_scan_compact(sa, st, e->device) : launch_scan(sa, st, e->device, local);
     if (run.prof) {
         HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used + 1], st));
         e->ev_scan_used += 2;
@@ -2047,9 +2083,12 @@ void stretch_report(swp_batch* b, const R6Run& run, const R6Stretch& s) {
 RoundRules stretch_rules(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t start, uint32_t end) {
     const uint32_t N = e->n_nodes, Wn = n_words_of(N);
     const bool cpt_allowed = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, run.block, run.nrr, true, run.shape.win) <= R6_LDS_BUDGET && b->csi_set.empty();
-    const bool scan_ok = N <= scan_max_nodes() && run.knobs.scan && b->csi_set.empty() && !b->wide_keys;
+    // (a cluster of more nodes than its workgroup's LDS holds: conditionally, stretch by stretch — the union of the stretch's class rows must fit)
+    const bool scan_whole = N <= scan_max_nodes();
+    const bool scan_ok = (scan_whole || run.knobs.scan_compact) && run.knobs.scan && b->csi_set.empty() && !b->wide_keys;
     const bool scan_fast = ra.n_rg == 0 && ra.csi_of == nullptr && scan_batched_fits(N, b->n_svc, b->n_sc);
-    return RoundRules{RoundPace(end - start, run.block, run.knobs.block_forced, start), CompactSwitch(cpt_allowed, run.knobs, e->r6_compact_hint), ScanHandover(scan_ok, scan_fast), !run.shape.runs};
+    return RoundRules{RoundPace(end - start, run.block, run.knobs.block_forced, start), CompactSwitch(cpt_allowed, run.knobs, e->r6_compact_hint),
+                      scan_whole ? ScanHandover(scan_ok, scan_fast) : ScanHandover::conditional(scan_ok, scan_max_nodes()), !run.shape.runs};
 }
 
 // On the stream: the stretch's position and end, the bitmaps built from the node rows as they are.
@@ -2098,9 +2137,23 @@ int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_
         bool to_scan = s.rules.after_rounds(r6_words(hb), &used, &recent);
         if (dbg_bits & 32) fprintf(stderr, "[swp] chunk: %u rounds, %.1f tasks each, at %u of %u | block %u compact %u csize %u clevel %u base %u maxrel %u\n", used, recent, pace.pos, end, s.ra.block, s.ra.compact, hb.csize, hb.clevel, hb.base, hb.maxrel);
         while (to_scan) {   // a scan stretch, and another directly behind it while the rules say so
-            const uint32_t upto = s.rules.scan_upto();
+            uint32_t upto = s.rules.scan_upto(), union_nodes = 0;
+            if (s.rules.scan.probed) {   // a cluster beyond the scan resolver's node count: only a stretch whose class rows' union fits, at most one shorter try
+                for (int attempt = 0; attempt < 2; ++attempt) {
+                    ++s.rules.scan.probes;
+                    if (int rc = scan_probe(e, b, run, s.ra, pace.pos, upto, &union_nodes)) return rc;
+                    if (dbg_bits & 32) fprintf(stderr, "[swp] scan probe: the class rows of tasks [%u, %u) cover %u nodes\n", pace.pos, upto, union_nodes);
+                    const uint32_t shorter = s.rules.scan.shorter(pace.pos, upto);
+                    if (s.rules.scan.fits(union_nodes) || shorter >= upto) break;
+                    if (attempt == 0) upto = shorter;
+                }
+                if (!s.rules.scan.fits(union_nodes)) {
+                    s.rules.scan_refused(recent);
+                    break;
+                }
+            }
             bool node_local = false;
-            if (int rc = scan_stretch(e, b, run, s.ra, pace.pos, upto, &node_local)) return rc;
+            if (int rc = scan_stretch(e, b, run, s.ra, pace.pos, upto, &node_local, union_nodes)) return rc;
             const bool looks = s.rules.scan.looks(node_local, upto, end, (dbg_bits & 16) != 0);
             if (looks)
                 if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;

@@ -171,4 +171,37 @@ hipError_t launch_scan(const ScanArgs& s, hipStream_t st, int dev, bool node_loc
     return launch_scan_nq<false>(s, scan_lds(s.a.n_nodes), st, dev);
 }
 
+// ---- the compact instance: a cluster beyond SCAN_MAXN nodes, a stretch whose class rows' union is not ----
+// the probe: which class rows the tasks [j0, j1) name, their union, its node count (*s.cnc: the caller reads it), prefix sums and map
+hipError_t launch_scan_probe(const ScanArgs& s, hipStream_t st) {
+    hipError_t r = hipMemsetAsync(s.cused, 0, (size_t)s.n_sc * 4, st);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(k_scan_mark, dim3(std::min<uint32_t>(64u, (s.j1 - s.j0 + 255u) / 256u)), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(k_scan_union, dim3(1), dim3(SCAN_THREADS), scan_union_lds(), st, s);
+    return hipGetLastError();
+}
+template <int NQ, bool LM>
+static hipError_t launch_scan_c_as(const ScanArgs& s, size_t lds, hipStream_t st, int dev) {
+    hipError_t r;
+    if (lds > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(&k_scan<NQ, LM, true>), dev)) != hipSuccess) return r;
+    hipLaunchKernelGGL((k_scan<NQ, LM, true>), dim3(1), dim3(SCAN_THREADS), lds, st, s);
+    return hipGetLastError();
+}
+template <bool LM>
+static hipError_t launch_scan_c_nq(const ScanArgs& s, size_t lds, hipStream_t st, int dev) {
+    switch (scan_nq(s.n_c)) {
+        case 1: return launch_scan_c_as<1, LM>(s, lds, st, dev);
+        case 2: return launch_scan_c_as<2, LM>(s, lds, st, dev);
+        default: return launch_scan_c_as<4, LM>(s, lds, st, dev);
+    }
+}
+// the stretch behind a probe that found s.n_c <= SCAN_MAXN nodes: matrices of n_c columns, the one-task-a-barrier instance over them
+hipError_t launch_scan_compact(const ScanArgs& s, hipStream_t st, int dev) {
+    if (s.n_c == 0 || s.n_c > SCAN_MAXN) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scan_fill_c, dim3(1024), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(k_scan_lists_c, dim3(64, s.n_svc), dim3(256), 0, st, s);
+    if (scan_matrices_in_lds(s.n_c, s.n_svc)) return launch_scan_c_nq<true>(s, scan_lds_lm(s.n_c, s.n_svc), st, dev);
+    return launch_scan_c_nq<false>(s, scan_lds(s.n_c), st, dev);
+}
+
 }  // namespace swpdev

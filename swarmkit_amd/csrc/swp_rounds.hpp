@@ -23,6 +23,7 @@ struct R6Knobs {
     int compact = -1;            // SWP_R6_COMPACT: -1 unset (the rounds' symptom decides: CompactSwitch), 0 never, 1 from the first round on
     bool compact_fused = true;   // SWP_R6_COMPACT_FUSED=0: the index of the next round by a launch of its own, not at the end of k_r6_commit_c
     bool scan = true;            // SWP_SCAN=0: never hand a stretch to the scan resolver
+    bool scan_compact = true;    // SWP_SCAN_COMPACT=0: nor, on a cluster beyond the scan resolver's node count, one whose class rows' union would fit (no probe)
     bool twins = true;           // SWP_R6_TWINS=0: every list starts at its level's first candidate
     int levels = -1;             // SWP_R6_LEVELS: -1 unset and 1: lists over two levels where the rule allows them (r6_levels2), 0: never
 };
@@ -42,6 +43,7 @@ inline R6Knobs r6_knobs(uint32_t block_max, uint32_t default_cap) {
     k.compact = r6_knob01("SWP_R6_COMPACT");
     k.compact_fused = r6_knob01("SWP_R6_COMPACT_FUSED") != 0;
     k.scan = r6_knob01("SWP_SCAN") != 0;
+    k.scan_compact = r6_knob01("SWP_SCAN_COMPACT") != 0;
     k.twins = r6_knob01("SWP_R6_TWINS") != 0;
     k.levels = r6_knob01("SWP_R6_LEVELS");
     return k;
@@ -159,16 +161,46 @@ struct CompactSwitch {
 // barrier and answers an unplaceable task's twins without a look: where it can run (`fast`), a stretch goes to it after four poor
 // rounds and two probing rounds follow it; the one-task-a-barrier instance (~1 us a task) has to be worth more: eight poor rounds,
 // four probes. (Sixteen rounds of ~40 us between two stretches were a sixth of the dense batch.)
+//
+// CONDITIONAL (`probed`: a cluster of more nodes than the scan resolver takes): a stretch may go only if the union of its tasks' static
+// class rows has at most `max_nodes` nodes (swp_scan.hpp, the compact instance). The driver probes [pos, upto) when due() says so — two
+// small launches and one read-back — and asks fits(); too wide, it may try ONCE with shorter() (an eighth, at least 64 tasks: a
+// service-major batch has one pool at a time, a round-robin batch over many pools does not); refused() otherwise, and the rounds carry on
+// as they would have. A refused probe is not repeated at every look: the next one waits until the rounds have decided `hold` more tasks,
+// and `hold` doubles with every refusal (2 048, 4 096, ...) and never shrinks. T tasks of rounds that can never be scanned so pay at
+// most ceil(log2(T / 2048 + 1)) refusals of at most two probes each: 8 probes at T = 20 000, 18 at a million. While a refusal holds, the
+// chunks are not shortened either (cap_chunk): the rounds look as often as they would without a scan resolver.
 struct ScanHandover {
     bool ok, fast;
+    bool probed = false;       // the hand-over is conditional (above); `fast` is off then: the batched instance has no compact form
+    uint32_t max_nodes = 0;
+    uint32_t hold = 2048, hold_until = 0;   // after a refusal: no probe before the rounds have reached task hold_until
+    uint32_t probes = 0, refusals = 0;      // probes enqueued (the driver counts), stretches refused
     uint32_t len = 2048;       // tasks of the next stretch: still no plain candidates afterwards, and it is twice as long
     bool after_scan = false;   // the rounds since the last stretch: a few of them say whether the tasks still have no plain candidates
     uint32_t skipped_seen = 0, scanned = 0;
     ScanHandover(bool ok_, bool fast_) : ok(ok_), fast(ok_ && fast_) {}
-    bool due(uint32_t used, double recent, uint32_t left) const { return ok && used >= (fast ? (after_scan ? 2u : 4u) : (after_scan ? 4u : 8u)) && recent < 8.0 && left >= 64; }
+    static ScanHandover conditional(bool ok_, uint32_t max_nodes_) {
+        ScanHandover s(ok_, false);
+        s.probed = true;
+        s.max_nodes = max_nodes_;
+        return s;
+    }
+    bool held(uint32_t pos) const { return probed && pos < hold_until; }
+    bool due(uint32_t used, double recent, uint32_t left, uint32_t pos = 0xFFFFFFFFu) const {
+        return ok && !held(pos) && used >= (fast ? (after_scan ? 2u : 4u) : (after_scan ? 4u : 8u)) && recent < 8.0 && left >= 64;
+    }
+    bool fits(uint32_t union_nodes) const { return union_nodes >= 1 && union_nodes <= max_nodes; }
+    uint32_t shorter(uint32_t pos, uint32_t upto) const { return pos + std::max<uint32_t>(64u, (upto - pos) / 8u); }   // (due(): at least 64 tasks are left; never beyond upto)
+    void refused(uint32_t pos) {
+        ++refusals;
+        hold_until = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, (uint64_t)pos + hold);
+        hold = std::min<uint32_t>(hold * 2u, 1u << 30);
+    }
     uint32_t upto(uint32_t pos, uint32_t end) const { return (uint32_t)std::min<uint64_t>(end, (uint64_t)pos + len); }
     uint32_t took(uint32_t pos, uint32_t upto) {   // the stretch [pos, upto) was enqueued -> the probing rounds behind it
         scanned += upto - pos;
+        if (probed) len = std::max<uint32_t>(upto - pos, 64u);   // (where only a shorter stretch fitted, the next one is twice THAT long)
         len = std::min<uint32_t>(len * 2, 1u << 20);
         after_scan = true;
         return fast ? 2u : 4u;
@@ -182,7 +214,11 @@ struct ScanHandover {
         skipped_seen = scan_skipped;
         return upto < end && 2 * (uint64_t)sk >= upto - pos;
     }
-    uint32_t cap_chunk(uint32_t chunk, double recent) const {   // look again soon: rounds that hit such a stretch decide one task each
+    // look again soon: rounds that hit such a stretch decide one task each. Conditional: only rounds that ARE poor look sooner (sixteen
+    // of them decide fewer than 256 tasks) — a batch that is doing well is left the chunks it would have without a scan resolver — and
+    // none while a refusal holds.
+    uint32_t cap_chunk(uint32_t chunk, double recent, uint32_t pos = 0xFFFFFFFFu) const {
+        if (probed) return (ok && !held(pos) && recent < 16.0) ? std::min<uint32_t>(chunk, 16u) : chunk;
         return !ok ? chunk : std::min<uint32_t>(chunk, fast ? (recent < 16.0 ? 8u : recent < 64.0 ? 16u : 256u) : (recent < 16.0 ? 16u : recent < 64.0 ? 48u : 256u));
     }
 };
@@ -203,11 +239,19 @@ struct RoundRules {
         *used = w.rounds - pace.rounds_seen;
         *recent = pace.observe(w.pos, w.rounds);
         cpt.feed(*used, *recent, block, w);
-        if (scan.due(*used, *recent, pace.end - pace.pos)) return true;
-        scan.after_scan = false;
-        pace.replan(*recent);
-        pace.chunk = scan.cap_chunk(pace.chunk, *recent);
+        if (scan.due(*used, *recent, pace.end - pace.pos, pace.pos)) return true;
+        plan_rounds(*recent);
         return false;
+    }
+    void plan_rounds(double recent) {
+        scan.after_scan = false;
+        pace.replan(recent);
+        pace.chunk = scan.cap_chunk(pace.chunk, recent, pace.pos);
+    }
+    // the probe found the stretch, and a shorter one, too wide: the rounds carry on as if after_rounds had said false
+    void scan_refused(double recent) {
+        scan.refused(pace.pos);
+        plan_rounds(recent);
     }
     uint32_t scan_upto() const { return scan.upto(pace.pos, pace.end); }
     // The stretch [pace.pos, upto) was enqueued; `looked`: the words behind it, or null where scan.looks said no. true: another one.

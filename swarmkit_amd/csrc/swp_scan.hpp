@@ -14,6 +14,17 @@
 // 24-31, ActiveTasksCountByService in bits 0-23 — and the service's list entry of the node sit in two dense matrices in global memory
 // (built from the lists by k_scan_prep; a node is only ever looked at by the one thread that owns it, so nothing there is shared).
 // Written against swp_wave.hpp only (tests/emu/emu_scan.cpp runs it on CPU fibers against the sequential model).
+//
+// The COMPACT instance (k_scan<.., .., true>): a cluster of more than SCAN_MAXN nodes. Inside a stretch a node whose bit is clear in the
+// static class row of EVERY task of the stretch fails valid / Ready / Constraint / Platform / Plugin for all of them: it is never picked,
+// never changes and nobody reads it, so the argmin over all nodes is the argmin over the UNION of the stretch's class rows. When that
+// union has at most SCAN_MAXN nodes (a burst of services constrained to one labelled pool), the stretch runs on a compact node space
+// c in [0, n_c) with an ASCENDING map cmap[c] = node: the LDS rows, the matrices and the key's low 12 bits carry c — the lowest c among
+// equal keys is the lowest node —, everything that leaves the kernel (out_node, the log, list entries, the X row, the port maps, the
+// generic counts) the real node, which a thread keeps in registers for the stretch. k_scan_mark + k_scan_union build union, prefix sums
+// and map (the PROBE: the host reads n_c before it decides), k_scan_fill_c / k_scan_lists_c the matrices over n_c columns; a list
+// entry of a node outside the union is skipped — no task of the stretch can take that node, so the entry is neither read nor changed.
+// The batched instance (k_scanb) has no compact form yet. tests/emu/emu_scan_compact.cpp runs all of it against the model over ALL nodes.
 #pragma once
 #include "swp_resolve6.hpp"
 
@@ -37,7 +48,17 @@ struct ScanArgs {
     u32 n_svc, n_sc;   // services of the batch; static class rows (k_scanb keeps them in LDS)
     u32* hmat;         // [n_svc][n_nodes] (failures >= 5 ? failures : 0) << 24 | ActiveTasksCountByService
     u32* emat;         // [n_svc][n_nodes] list entry of (service, node), LIST_EMPTY: none
+    // the compact instance and its probe ([n_svc][n_c] matrices then); all null / 0 for the plain instances
+    u32 n_c;           // nodes of the union, <= SCAN_MAXN when a stretch is launched
+    u32* cused;        // [n_sc] != 0: a task of the stretch names the class row (zeroed by the launcher, set by k_scan_mark)
+    u64* cu;           // [n_words] the union of those rows
+    u32* cpre;         // [n_words] union bits in the words in front
+    u32* cmap;         // [SCAN_MAXN] compact index -> node, ascending (a union beyond SCAN_MAXN nodes is counted, not mapped)
+    u32* cnc;          // [1] the union's node count: what the host reads
 };
+// node -> compact index (the node's bit is set in the union)
+inline __host__ __device__ u32 scan_c_of(const u64* cu, const u32* cpre, u32 n) { return cpre[n >> 6] + (u32)__builtin_popcountll(cu[n >> 6] & ((1ull << (n & 63)) - 1ull)); }
+inline __host__ __device__ size_t scan_union_lds() { return 16 * 4; }   // k_scan_union: a word per wave
 #define SCAN_RTQ 32         // task records staged through LDS at a time (their loads are misses: a record is read once)
 inline __host__ __device__ size_t scan_lds(u32 n_nodes) { return (size_t)n_nodes * 24 + 16 * 16 + 64 + 2 * SCAN_RTQ * 64; }
 // ... plus the two (service, node) matrices when they fit next to it (SCAN_LM instances): a task then reads nothing but its static-class words from global memory
@@ -104,11 +125,72 @@ WV_KERNEL(256) void k_scan_lists(ScanArgs s) {
     }
 }
 
+// ---- the compact instance's probe and matrices
+// the class rows the tasks [j0, j1) name (cused zeroed before): grid-stride, any grid
+WV_KERNEL(256) void k_scan_mark(ScanArgs s) {
+    for (u32 t = s.j0 + wv::block() * 256 + wv::tid(); t < s.j1; t += 256u * 64u) s.cused[s.a.rt[t].sc] = 1u;
+}
+// ONE workgroup: the union of the marked rows, its node count, the prefix sums over its words and the map. A thread takes a run of
+// consecutive words, so that its bits follow those of the threads in front: the map comes out ascending.
+WV_KERNEL(SCAN_THREADS) void k_scan_union(ScanArgs s) {
+    const u32 tid = wv::tid(), Wn = s.a.n_words;
+    u32* wsum = reinterpret_cast<u32*>(wv::lds());   // [16] bits of each wave's words
+    const u32 per = (Wn + SCAN_THREADS - 1u) / SCAN_THREADS, w0 = tid * per, w1 = w0 + per < Wn ? w0 + per : Wn;
+    u32 cnt = 0;
+    for (u32 w = w0; w < w1; ++w) {
+        u64 u = 0;
+        for (u32 c = 0; c < s.n_sc; ++c)
+            if (s.cused[c]) u |= s.a.sc[(size_t)c * Wn + w];
+        s.cu[w] = u;
+        cnt += (u32)wv::popc64(u);
+    }
+    const u32 incl = wv::scan_incl_u32(cnt);
+    if (wv::lane() == 63) wsum[tid >> 6] = incl;
+    wv::barrier();
+    u32 base = incl - cnt, all = 0;
+    for (u32 v = 0; v < SCAN_THREADS / 64; ++v) {
+        const u32 x = wsum[v];
+        if (v < (tid >> 6)) base += x;
+        all += x;
+    }
+    for (u32 w = w0; w < w1; ++w) {
+        u64 u = s.cu[w];   // (this thread's own store)
+        s.cpre[w] = base;
+        while (u) {
+            if (base < SCAN_MAXN) s.cmap[base] = w * 64u + (u32)wv::ffs64(u);
+            ++base;
+            u &= u - 1ull;
+        }
+    }
+    if (tid == 0) *s.cnc = all;
+}
+WV_KERNEL(256) void k_scan_fill_c(ScanArgs s) {
+    const size_t n = (size_t)s.n_svc * s.n_c;
+    for (size_t i = (size_t)wv::block() * 256 + wv::tid(); i < n; i += (size_t)256 * 1024) {
+        s.hmat[i] = 0;
+        s.emat[i] = LIST_EMPTY;
+    }
+}
+WV_KERNEL(256) void k_scan_lists_c(ScanArgs s) {
+    const u32 svc = wv::block_y();
+    const u32 e0 = s.a.list_off[svc], e1 = s.a.list_off[svc + 1];
+    for (u32 e = e0 + wv::block() * 256 + wv::tid(); e < e1; e += 256u * 64u) {
+        const u32 n = s.a.list_node[e];
+        if (n == LIST_EMPTY || !((s.cu[n >> 6] >> (n & 63)) & 1ull)) continue;   // (outside the union: no task of the stretch can take the node)
+        const u32 c = scan_c_of(s.cu, s.cpre, n);
+        const u32 fl = s.a.list_fail[e], sv = s.a.list_svc[e];
+        if (fl >= 256u || sv >= (1u << 24)) s.a.blk->error = ERR_GROUP_RANGE;
+        s.hmat[(size_t)svc * s.n_c + c] = ((fl >= MAX_FAILURES ? fl : 0u) << 24) | sv;
+        s.emat[(size_t)svc * s.n_c + c] = e;
+    }
+}
+
 // SCAN_NQ: nodes per thread (the launcher instantiates 1, 2 and 4 — scan_nq: a thread of a 1 000-node scan carries no code for nodes it has not)
-template <int SCAN_NQ, bool SCAN_LM>
+// SCAN_CM: the compact instance — N is the union's node count, a row index a compact one, `real` the node behind it; false: today's code
+template <int SCAN_NQ, bool SCAN_LM, bool SCAN_CM = false>
 WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
     const R6Args& a = s.a;
-    const u32 tid = wv::tid(), lane = wv::lane(), N = a.n_nodes, Wn = a.n_words;
+    const u32 tid = wv::tid(), lane = wv::lane(), N = SCAN_CM ? s.n_c : a.n_nodes, Wn = a.n_words;
     unsigned char* l = reinterpret_cast<unsigned char*>(wv::lds());
     i64* cpu = reinterpret_cast<i64*>(l);
     i64* mem = cpu + N;
@@ -120,7 +202,21 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
     u32* hm = reinterpret_cast<u32*>(l + ((scan_lds(N) + 15) & ~(size_t)15));           // SCAN_LM: [n_svc][N] the key halves ...
     u32* em = hm + (size_t)s.n_svc * N;                                                  // ... and the list entries, here instead of in global memory
     if (a.blk->error != ERR_NONE) return;
-    for (u32 n = tid; n < N; n += SCAN_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
+    u32 real[SCAN_NQ];   // this thread's nodes: fixed for the stretch
+    WV_UNROLL
+    for (int q = 0; q < SCAN_NQ; ++q) {
+        const u32 n = tid + (u32)q * SCAN_THREADS;
+        real[q] = (SCAN_CM && n < N) ? s.cmap[n] : n;
+    }
+    if (!SCAN_CM)
+        for (u32 n = tid; n < N; n += SCAN_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
+    else {
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS, m = real[q];
+            if (n < N) { cpu[n] = a.cpu[m]; mem[n] = a.mem[m]; tot[n] = a.total[m]; lastc[n] = a.last[m]; }
+        }
+    }
     if (SCAN_LM)
         for (u32 x = tid; x < s.n_svc * N; x += SCAN_THREADS) { hm[x] = s.hmat[x]; em[x] = s.emat[x]; }
     u32 nc = a.ctl->ncommit, ni = a.ctl->ninf;
@@ -150,7 +246,7 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
     WV_UNROLL
     for (int q = 0; q < SCAN_NQ; ++q) {
         const u32 n = tid + (u32)q * SCAN_THREADS;
-        scn[q] = n < N ? a.sc[(size_t)rn.sc * Wn + (n >> 6)] : 0ull;
+        scn[q] = n < N ? a.sc[(size_t)rn.sc * Wn + (real[q] >> 6)] : 0ull;
         hin[q] = (!SCAN_LM && n < N) ? s.hmat[(size_t)rn.svc * N + n] : 0u;
         ein[q] = (!SCAN_LM && n < N) ? s.emat[(size_t)rn.svc * N + n] : LIST_EMPTY;
     }
@@ -171,7 +267,7 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
             WV_UNROLL
             for (int q = 0; q < SCAN_NQ; ++q) {
                 const u32 n = tid + (u32)q * SCAN_THREADS;
-                scn[q] = n < N ? a.sc[(size_t)rn.sc * Wn + (n >> 6)] : 0ull;
+                scn[q] = n < N ? a.sc[(size_t)rn.sc * Wn + (real[q] >> 6)] : 0ull;
                 hin[q] = (!SCAN_LM && n < N) ? s.hmat[(size_t)rn.svc * N + n] : 0u;
                 ein[q] = (!SCAN_LM && n < N) ? s.emat[(size_t)rn.svc * N + n] : LIST_EMPTY;
             }
@@ -183,8 +279,8 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
         for (int q = 0; q < SCAN_NQ; ++q) {
             const u32 n = tid + (u32)q * SCAN_THREADS;
             if (n >= N) continue;
-            const u32 w = n >> 6;
-            const u64 bit = 1ull << (n & 63);
+            const u32 m = real[q], w = m >> 6;
+            const u64 bit = 1ull << (m & 63);
             if (!(scw[q] & bit)) continue;   // (the static class row holds valid & ready & constraints & platform & plugins)
             const u32 hi = SCAN_LM ? hm[(size_t)r.svc * N + n] : hiw[q];
             if ((r.flags & RT_RES) && !(r.cpu <= cpu[n] && r.mem <= mem[n])) continue;
@@ -192,7 +288,7 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
             if (gset)
                 for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) {
                     const u32 row = a.gs_row[g];
-                    if (a.gcnt[(size_t)a.rg_kind[row] * a.gstride + n] < a.rg_val[row]) ok = false;   // HasEnough, validate.go:24-52
+                    if (a.gcnt[(size_t)a.rg_kind[row] * a.gstride + m] < a.rg_val[row]) ok = false;   // HasEnough, validate.go:24-52
                 }
             if (ok && (r.flags & RT_PORTS))
                 for (u32 z = a.pset_off[r.pset]; z < a.pset_off[r.pset + 1]; ++z)
@@ -224,12 +320,19 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
             ++ni;
         } else {
             if ((gn & (SCAN_THREADS - 1u)) == tid) {
-                const u32 nd = gn, w = nd >> 6;
-                const u64 bit = 1ull << (nd & 63);
+                const u32 nd = gn;
+                u32 m = nd;   // the node behind the row
+                if (SCAN_CM) {
+                    WV_UNROLL
+                    for (int q = 0; q < SCAN_NQ; ++q)
+                        if (tid + (u32)q * SCAN_THREADS == nd) m = real[q];
+                }
+                const u32 w = m >> 6;
+                const u64 bit = 1ull << (m & 63);
                 if (r.cpu) cpu[nd] -= r.cpu;
                 if (r.mem) mem[nd] -= r.mem;
                 if (gset)
-                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) a.gcnt[(size_t)a.rg_kind[a.gs_row[g]] * a.gstride + nd] -= a.rg_val[a.gs_row[g]];   // Claim
+                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) a.gcnt[(size_t)a.rg_kind[a.gs_row[g]] * a.gstride + m] -= a.rg_val[a.gs_row[g]];   // Claim
                 if (r.flags & RT_PORTS)
                     for (u32 q = a.pset_off[r.pset]; q < a.pset_off[r.pset + 1]; ++q) wv::g_or64(a.portmap + (size_t)a.pset_ids[q] * Wn + w, bit);
                 if (!(r.flags & RT_UNCOUNTED)) {
@@ -249,7 +352,7 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
                     else s.hmat[(size_t)r.svc * N + nd] = hi;
                     if (entry == LIST_EMPTY) {
                         wv::g_or64(a.X + (size_t)r.svc * a.xs + w, bit);
-                        a.list_node[r.slot] = nd;
+                        a.list_node[r.slot] = m;
                         a.list_svc[r.slot] = 1;
                         a.list_fail[r.slot] = 0;
                         if (SCAN_LM) em[(size_t)r.svc * N + nd] = r.slot;
@@ -264,17 +367,25 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
                     }
                 }
                 const int32_t prev = lastc[nd];
-                a.log_node[nc] = nd;
+                a.log_node[nc] = m;
                 a.log_task[nc] = t;
                 a.log_prev[nc] = prev;
                 lastc[nd] = (int32_t)nc;
-                a.out_node[t] = (int32_t)nd;
+                a.out_node[t] = (int32_t)m;
             }
             ++nc;
         }
         // (no second barrier: a node's row is read and written by its owner only, the records of a chunk are staged behind a barrier of their own)
     }
-    for (u32 n = tid; n < N; n += SCAN_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    if (!SCAN_CM)
+        for (u32 n = tid; n < N; n += SCAN_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    else {
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS, m = real[q];
+            if (n < N) { a.cpu[m] = cpu[n]; a.mem[m] = mem[n]; a.total[m] = tot[n]; a.last[m] = lastc[n]; }
+        }
+    }
     if (tid == 0) {
         a.ctl->ncommit = nc;
         a.ctl->ninf = ni;
