@@ -656,6 +656,11 @@ typedef struct {
                                    counts those stretches and ms_scan their time (SWP_CFG_PROFILE). A stretch that went through the compact
                                    instance — a cluster of more than 4 096 nodes, the union of the stretch's class rows at most that — is
                                    counted like any other, in both; a probe that refused a stretch is counted in neither */
+    uint32_t scan_batched_tasks;   /* last batch: ... of them the tasks of the stretches the batched instance took (k_scanb, several tasks a
+                                      barrier: no host ports, generic reservations or cluster mounts in the stretch, and its rows — over all
+                                      nodes, or over the union of a compact stretch — fit in LDS); plain and compact stretches alike */
+    uint32_t scan_skipped;         /* last batch: tasks of those stretches answered "no node" without a look (an identical task had found
+                                      none earlier in its stretch): a saturated pool's backlog */
 } swp_stats_t;
 
 int swp_create(const swp_config*, swp_engine** out);

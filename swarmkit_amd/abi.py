@@ -74,7 +74,8 @@ class Stats(C.Structure):
                 ("ms_classes", C.c_float), ("ms_scan", C.c_float), ("ms_resolve", C.c_float), ("ms_explain", C.c_float), ("ms_total", C.c_float),
                 ("scan_launches", C.c_uint32), ("resolve_launches", C.c_uint32), ("last_resolver", C.c_uint32),
                 ("ms_propose", C.c_float), ("ms_apply", C.c_float), ("propose_launches", C.c_uint32), ("propose_tasks", C.c_uint32),
-                ("waterfill_tasks", C.c_uint32), ("scan_tasks", C.c_uint32)]
+                ("waterfill_tasks", C.c_uint32), ("scan_tasks", C.c_uint32),
+                ("scan_batched_tasks", C.c_uint32), ("scan_skipped", C.c_uint32)]
 
 
 # numpy views of the POD structs, for bulk construction
@@ -159,8 +160,10 @@ def build_library(force=False):
 _libs = {}
 
 
-def load_library(path=None):
-    """libswp.so (default) or another library with the same exports (tests/_build/libswpfake.so: the host layer's CPU test double)."""
+def load_library(path=None, earlier_stats=False):
+    """libswp.so (default) or another library with the same exports (tests/_build/libswpfake.so: the host layer's CPU test double).
+    earlier_stats: the library may be an EARLIER commit's (the same-box A/B tools' --parent) — swp_stats_t only ever grows by counters
+    appended at its end, so such a library may report a shorter one; swp_stats fills a prefix and the counters behind it read 0."""
     path = path or LIB_PATH
     if path in _libs:
         return _libs[path]
@@ -271,6 +274,8 @@ def load_library(path=None):
     sizes = (u32 * 16)()
     n = L.swp_abi_check(sizes, 16)
     want = [C.sizeof(x) for x in (Config, NodeRow, KV, Constraint, Platform, Port, TaskDesc, Placement, Stats, Spread, Generic)]
+    if earlier_stats and n == len(want) and sizes[8] < want[8]:
+        sizes[8] = want[8]
     if list(sizes[:n]) != want:
         raise RuntimeError(f"ABI struct size mismatch: lib {list(sizes[:n])} vs binding {want}")
     _libs[path] = L
@@ -397,11 +402,11 @@ class Engine:
     """One swp_engine handle. Raises SwpError(SWP_ENODEVICE) when no gfx950 is present: there is no CPU path."""
 
     def __init__(self, device=0, resolver_threads=0, profile=False, lib_path=None, shard_rank=0, shard_count=0,
-                 shards=None, nodes_per_shard=None, devices=None):
+                 shards=None, nodes_per_shard=None, devices=None, earlier_stats=False):
         """shards=G, nodes_per_shard=cap: a shard SET (swp_shardset_create) — G engines of this process behind the one handle, on
         `devices` (one ordinal per shard; default: all on `device`). SWP_SHARDSET="G:cap" in the environment turns every engine
         created without shard arguments into such a set (how the whole scenario suite is run over node-range shards)."""
-        self.L = load_library(lib_path)
+        self.L = load_library(lib_path, earlier_stats)
         cfg = Config(device=device, resolver_threads=resolver_threads, flags=CFG_PROFILE if profile else 0,
                      shard_rank=shard_rank, shard_count=shard_count)
         env = os.environ.get("SWP_SHARDSET")

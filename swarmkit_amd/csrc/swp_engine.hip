@@ -576,6 +576,7 @@ struct swp_engine {
 
     std::vector<hipEvent_t> ev_scan;   // SWP_CFG_PROFILE: a pair per stretch the scan resolver took (scan_stretch); ev_scan_used of them in this batch
     uint32_t ev_scan_used = 0, scan_tasks_batch = 0, scan_stretches_batch = 0;
+    uint32_t scan_batched_batch = 0, scan_skipped_batch = 0;   // ... of them by k_scanb; tasks it answered without a look
     bool r6_compact_hint = false;   // the last batch's rounds used a compact index (re-placements after a drain): the next one starts with it
     swp_stats_t stats{};
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1999,9 +2000,10 @@ int scan_probe(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, 
 // The tasks [pos, upto) to the scan resolver, one after the other (swp_scan.hpp); behind it the bitmaps rebuilt — the rounds go on from
 // the rows as the scan left them — and, streamed, a publish (the scan kernels leave Blk6.pos at the end of their stretch).
 // *node_local: k_scanb could take it (every input of a task in LDS, every effect on ONE node).
-// union_nodes != 0: through the compact instance, over the union the probe of [pos, upto) left in the batch's buffers (never node_local:
-// the batched instance has no compact form).
-int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t pos, uint32_t upto, bool* node_local, uint32_t union_nodes = 0) {
+// union_nodes != 0: through the compact instance, over the union the probe of [pos, upto) left in the batch's buffers.
+// *batched: the stretch went through k_scanb (the control block's scan_skipped moves). On a compact stretch only the probe tells, so
+// there it is the stretch's property (ScanHandover::looks' stretch_fast), not the rules'.
+int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t pos, uint32_t upto, bool* node_local, uint32_t union_nodes = 0, bool* batched = nullptr) {
     hipStream_t st = e->stream;
     ScanArgs sa{};
     sa.a = ra;
@@ -2014,10 +2016,12 @@ int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra
     sa.hmat = b->d_hmat.as<uint32_t>();
     sa.emat = b->d_emat.as<uint32_t>();
     sa.n_sc = b->n_sc;
-    bool local = ra.n_rg == 0 && ra.csi_of == nullptr && !union_nodes;
+    bool local = ra.n_rg == 0 && ra.csi_of == nullptr;
     for (uint32_t j = pos; j < upto && local; ++j)
         if (b->rt[j].flags & RT_PORTS) local = false;
+    const bool by_b = local && (union_nodes ? scan_batched_fits_c(union_nodes, b->n_svc, b->n_sc) : scan_batched_fits(e->n_nodes, b->n_svc, b->n_sc));   // (the launchers' rule)
     *node_local = local;
+    if (batched) *batched = by_b;
     if (union_nodes) {
         if (int rc = scan_compact_bufs(e, b, &sa)) return rc;
         sa.n_c = union_nodes;
@@ -2026,13 +2030,14 @@ int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra
         if (int rc = grow_events(e, e->ev_scan, (size_t)e->ev_scan_used + 2)) return rc;
         HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used], st));
     }
-    hipError_t r = union_nodes ? launch_scan_compact(sa, st, e->device) : launch_scan(sa, st, e->device, local);
+    hipError_t r = union_nodes ? launch_scan_compact(sa, st, e->device, local) : launch_scan(sa, st, e->device, local);
     if (run.prof) {
         HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used + 1], st));
         e->ev_scan_used += 2;
     }
     e->scan_tasks_batch += upto - pos;
     e->scan_stretches_batch += 1;
+    if (by_b) e->scan_batched_batch += upto - pos;
     if (r == hipSuccess) r = launch_r6_build(ra, st);
     if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan launch: %s", hipGetErrorString(r));
     if (run.sx)
@@ -2079,7 +2084,8 @@ void stretch_report(swp_batch* b, const R6Run& run, const R6Stretch& s) {
 
 // What the engine and the batch allow the rules of a stretch: no compact index that would need a smaller block, nor with volumes; the
 // scan resolver knows no volumes, and its keys hold 255 failures and 2^24 - 1 tasks of a service on a node; its batched instance
-// (k_scanb) knows no generic resources either, and a window's rows must fit its LDS.
+// (k_scanb) knows no generic resources either, and a window's rows must fit its LDS. On a cluster beyond the scan resolver's node
+// count the hand-over is conditional and whether a stretch is fast is known only behind its probe (scan_stretch's *node_local).
 RoundRules stretch_rules(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra, uint32_t start, uint32_t end) {
     const uint32_t N = e->n_nodes, Wn = n_words_of(N);
     const bool cpt_allowed = Wn <= R6_COMPACT_MAX_WORDS && r6_commit_lds_size(Wn, run.block, run.nrr, true, run.shape.win) <= R6_LDS_BUDGET && b->csi_set.empty();
@@ -2122,6 +2128,7 @@ int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_
     RoundPace& pace = s.rules.pace;
     Blk6& hb = s.hb;
     const uint32_t dbg_bits = run.knobs.dbg;
+    bool unread = false;   // a stretch went through k_scanb since the words were last read
     while (pace.pos < end) {
         s.ra.block = pace.block;
         s.ra.compact = s.rules.cpt.compact();
@@ -2129,6 +2136,7 @@ int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_
         s.ra.levels2 = r6_levels2(run.knobs, s.ra.ext != nullptr, s.ra.n_words, R6_LIST) ? 1u : 0u;
         if (int rc = launch_chunk(e, b, run.sx, s.ra, pace.chunk)) return rc;
         if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
+        unread = false;
         if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
         if (hb.error != ERR_NONE) return e->fail(SWP_ERANGE, "per-node task-count spread exceeds the %d level planes of the block resolver", R6_NP);
         if (hb.pos <= pace.pos) return e->fail(SWP_EHIP, "block resolver made no progress at task %u", pace.pos);   // a round decides its first task at least
@@ -2152,15 +2160,21 @@ int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_
                     break;
                 }
             }
-            bool node_local = false;
-            if (int rc = scan_stretch(e, b, run, s.ra, pace.pos, upto, &node_local, union_nodes)) return rc;
-            const bool looks = s.rules.scan.looks(node_local, upto, end, (dbg_bits & 16) != 0);
-            if (looks)
+            bool node_local = false, batched = false;
+            if (int rc = scan_stretch(e, b, run, s.ra, pace.pos, upto, &node_local, union_nodes, &batched)) return rc;
+            unread = unread || batched;
+            const bool looks = s.rules.scan.looks(node_local, upto, end, (dbg_bits & 16) != 0, batched && union_nodes != 0);
+            if (looks) {
                 if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
+                unread = false;
+            }
             const R6Words w = r6_words(hb);
             to_scan = s.rules.after_scan(upto, looks ? &w : nullptr);
         }
     }
+    if (unread)   // (the stretch ended on a scan stretch nobody looked behind: its count of skipped tasks for the stats)
+        if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
+    e->scan_skipped_batch += hb.scan_skipped;
     e->r6_compact_hint = s.rules.cpt.ever;
     run.rounds += hb.rounds;
     if (run.prof) HIPCHECK(e, hipEventRecord(e->ev_pool[4 * run.wi + 3], e->stream));
@@ -2205,6 +2219,8 @@ void batch_stats(swp_engine* e, swp_batch* b, const R6Run& run, const Ctl& ctl) 
         fprintf(stderr, "[swp] shader clock: %llu cycles / %llu x10ns => %.0f MHz\n", ctl.cyc[6], ctl.cyc[7], (double)ctl.cyc[6] / ((double)ctl.cyc[7] * 0.01));
     e->stats.scan_launches = e->scan_stretches_batch;
     e->stats.scan_tasks = e->scan_tasks_batch;
+    e->stats.scan_batched_tasks = e->scan_batched_batch;
+    e->stats.scan_skipped = e->scan_skipped_batch;
     e->stats.last_windows = run.wi;   // resolver stretches of this batch
     e->stats.last_static_classes = b->n_sc;
     e->stats.resolve_launches += (uint32_t)(2 * run.rounds);   // k_resolve6: a propose and a commit launch per round
@@ -2221,7 +2237,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     hipStream_t st = e->stream;
     if (run.prof) HIPCHECK(e, hipEventRecord(e->ev[0], st));
     e->ev_scan_used = 0;
-    e->scan_tasks_batch = e->scan_stretches_batch = 0;
+    e->scan_tasks_batch = e->scan_stretches_batch = e->scan_batched_batch = e->scan_skipped_batch = 0;
 
     int rc = batch_begin(e, b);
     if (rc) return rc;

@@ -58,7 +58,8 @@ uint32_t scan_max_nodes();
 bool scan_batched_fits(uint32_t n_nodes, uint32_t n_svc, uint32_t n_sc);   // k_scanb (several tasks a barrier, identical unplaceable tasks skipped) can take such a batch: everything it reads fits in LDS
 hipError_t launch_scan(const ScanArgs& s, hipStream_t st, int dev, bool node_local);
 hipError_t launch_scan_probe(const ScanArgs& s, hipStream_t st);                // the compact instance: the union of the stretch's class rows, *s.cnc its node count
-hipError_t launch_scan_compact(const ScanArgs& s, hipStream_t st, int dev);     // ... and the stretch over it (s.n_c as read from the probe, <= scan_max_nodes())
+bool scan_batched_fits_c(uint32_t n_c, uint32_t n_svc, uint32_t n_sc);          // ... k_scanb's compact form takes a node-local stretch over a union of n_c nodes: its rows fit in LDS and the union is small enough (or SWP_SCANB_COMPACT=1)
+hipError_t launch_scan_compact(const ScanArgs& s, hipStream_t st, int dev, bool node_local);   // ... and the stretch over it (s.n_c as read from the probe, <= scan_max_nodes()); node_local: as for launch_scan
 
 // task groups (swp_groups.hip)
 struct Groups2Args;

@@ -195,11 +195,40 @@ static hipError_t launch_scan_c_nq(const ScanArgs& s, size_t lds, hipStream_t st
         default: return launch_scan_c_as<4, LM>(s, lds, st, dev);
     }
 }
-// the stretch behind a probe that found s.n_c <= SCAN_MAXN nodes: matrices of n_c columns, the one-task-a-barrier instance over them
-hipError_t launch_scan_compact(const ScanArgs& s, hipStream_t st, int dev) {
+// The ONE rule for a compact stretch (the driver asks it, the launcher launches by it). Its rows over the union must fit in LDS; beyond
+// that the batched form is taken by default only for unions of at most SCANB_COMPACT_AUTO nodes — up to four nodes a thread, where a
+// batch's evaluation is what it is on the dense batch. Measured (profiles/scanb_compact.json): a pool of 1 237 nodes needs the
+// eight-nodes-a-thread instance and lost 9 ms of 73 to the one-task-a-barrier instance. SWP_SCANB_COMPACT=1: every union that fits
+// (tests, A/B runs), =0: none.
+#define SCANB_COMPACT_AUTO 1024u
+bool scan_batched_fits_c(uint32_t n_c, uint32_t n_svc, uint32_t n_sc) {
+    if (getenv("SWP_SCAN_UNBATCHED") || scan_lds_bc(n_c, n_svc, n_sc) > (size_t)160 * 1024 - 512) return false;
+    const char* env = getenv("SWP_SCANB_COMPACT");
+    return env ? atoi(env) != 0 : n_c <= SCANB_COMPACT_AUTO;
+}
+template <int NQ>
+static hipError_t launch_scanb_c_as(const ScanArgs& s, size_t lds, hipStream_t st, int dev) {
+    hipError_t r;
+    if (lds > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(&k_scanb<NQ, true>), dev)) != hipSuccess) return r;
+    hipLaunchKernelGGL((k_scanb<NQ, true>), dim3(1), dim3(SCANB_THREADS), lds, st, s);
+    return hipGetLastError();
+}
+// the stretch behind a probe that found s.n_c <= SCAN_MAXN nodes: matrices of n_c columns, and over them the batched instance where
+// the stretch is node_local (launch_scan) and its rows over n_c nodes fit in LDS, the one-task-a-barrier instance otherwise
+hipError_t launch_scan_compact(const ScanArgs& s, hipStream_t st, int dev, bool node_local) {
     if (s.n_c == 0 || s.n_c > SCAN_MAXN) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scan_fill_c, dim3(1024), dim3(256), 0, st, s);
     hipLaunchKernelGGL(k_scan_lists_c, dim3(64, s.n_svc), dim3(256), 0, st, s);
+    if (node_local && scan_batched_fits_c(s.n_c, s.n_svc, s.n_sc)) {
+        const size_t lds = scan_lds_bc(s.n_c, s.n_svc, s.n_sc);
+        switch (scanb_nq(s.n_c)) {
+            case 1: return launch_scanb_c_as<1>(s, lds, st, dev);
+            case 2: return launch_scanb_c_as<2>(s, lds, st, dev);
+            case 4: return launch_scanb_c_as<4>(s, lds, st, dev);
+            case 8: return launch_scanb_c_as<8>(s, lds, st, dev);
+            default: return launch_scanb_c_as<16>(s, lds, st, dev);
+        }
+    }
     if (scan_matrices_in_lds(s.n_c, s.n_svc)) return launch_scan_c_nq<true>(s, scan_lds_lm(s.n_c, s.n_svc), st, dev);
     return launch_scan_c_nq<false>(s, scan_lds(s.n_c), st, dev);
 }

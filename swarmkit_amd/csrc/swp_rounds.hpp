@@ -172,7 +172,7 @@ struct CompactSwitch {
 // chunks are not shortened either (cap_chunk): the rounds look as often as they would without a scan resolver.
 struct ScanHandover {
     bool ok, fast;
-    bool probed = false;       // the hand-over is conditional (above); `fast` is off then: the batched instance has no compact form
+    bool probed = false;       // the hand-over is conditional (above); `fast` is off then: whether the batched instance takes a stretch is known behind its probe (looks)
     uint32_t max_nodes = 0;
     uint32_t hold = 2048, hold_until = 0;   // after a refusal: no probe before the rounds have reached task hold_until
     uint32_t probes = 0, refusals = 0;      // probes enqueued (the driver counts), stretches refused
@@ -205,8 +205,10 @@ struct ScanHandover {
         after_scan = true;
         return fast ? 2u : 4u;
     }
-    // the words are read behind a node-local stretch of the batched instance: for `again`, and at the end for the driver's report only
-    bool looks(bool node_local, uint32_t upto, uint32_t end, bool report) const { return node_local && fast && (upto < end || report); }
+    // the words are read behind a node-local stretch of the batched instance: for `again`, and at the end for the driver's report only.
+    // stretch_fast: a conditional hand-over's stretch that the batched instance took — fast is the
+    // STRETCH's property then, not the rules'; the next stretch gets its own probe first (its union may differ).
+    bool looks(bool node_local, uint32_t upto, uint32_t end, bool report, bool stretch_fast = false) const { return node_local && (fast || (probed && ok && stretch_fast)) && (upto < end || report); }
     // Most of the stretch was answered without a look (identical tasks had found no node — a saturated cluster's backlog): the kernel
     // does that at a hundred tasks a microsecond, a round of the block resolver at ten. Another stretch directly behind this one.
     bool again(uint32_t pos, uint32_t upto, uint32_t end, uint32_t scan_skipped) {

@@ -24,7 +24,14 @@
 // generic counts) the real node, which a thread keeps in registers for the stretch. k_scan_mark + k_scan_union build union, prefix sums
 // and map (the PROBE: the host reads n_c before it decides), k_scan_fill_c / k_scan_lists_c the matrices over n_c columns; a list
 // entry of a node outside the union is skipped — no task of the stretch can take that node, so the entry is neither read nor changed.
-// The batched instance (k_scanb) has no compact form yet. tests/emu/emu_scan_compact.cpp runs all of it against the model over ALL nodes.
+// tests/emu/emu_scan_compact.cpp runs all of it against the model over ALL nodes.
+//
+// The COMPACT BATCHED instance (k_scanb<.., true>): the same compact space under the batched instance below, for a union whose rows fit
+// its LDS (scan_lds_bc; a larger one keeps k_scan<.., .., true>). Besides the node rows and the matrices its static class rows are
+// compact too — [n_sc][ceil(n_c / 64)] words, bit c of row r = bit cmap[c] of a.sc[r], gathered in the prologue (a wave per 64
+// consecutive c, one ballot per class row) — so a task still reads nothing from global memory. The batch's exactness argument does
+// not mention node numbers, and the tie rule holds as above (cmap ascending); the skip table, the windows and the unplaceable tasks'
+// places work in task space, which is not compacted. tests/emu/emu_scanb_compact.cpp runs it against the model over ALL nodes.
 #pragma once
 #include "swp_resolve6.hpp"
 
@@ -102,6 +109,8 @@ inline __host__ __device__ size_t scan_lds_b(u32 n_nodes, u32 n_svc, u32 n_sc) {
     return (((size_t)n_nodes * 24 + 15) & ~(size_t)15) + (size_t)2 * n_svc * n_nodes * 4 + (size_t)n_sc * ((n_nodes + 63) / 64) * 8 + 3 * SCAN_B * 8 +
            (SCAN_W / 64) * 8 + 16 + (size_t)SCAN_W * 64 + SCAN_W * 4 + SCAN_DT * 4;
 }
+// ... of the compact batched instance: every row — the nodes', the matrices', the class rows' words — is over the union's n_c nodes
+inline __host__ __device__ size_t scan_lds_bc(u32 n_c, u32 n_svc, u32 n_sc) { return scan_lds_b(n_c, n_svc, n_sc); }
 
 #ifdef SWP_SCAN_KERNELS
 // hmat / emat from the per-service lists: grid (entries of the longest list / 256, services)
@@ -392,10 +401,25 @@ WV_KERNEL(SCAN_THREADS) void k_scan(ScanArgs s) {
         a.blk->pos = s.j1;
     }
 }
-template <int SCAN_NQ>
+// The compact batched instance's class rows, by whole waves of a workgroup of SCANB_THREADS: rows[n_sc][ceil(n_c / 64)], bit c of row r =
+// bit cmap[c] of a.sc[r]. A wave takes 64 consecutive c; a ballot per row IS the row's word (bits beyond n_c are clear).
+WV_DEV void scanb_rows_c(const ScanArgs& s, u64* rows) {
+    const u32 lane = wv::lane(), N = s.n_c, Wn = s.a.n_words, Wl = (N + 63u) / 64u;
+    for (u32 w = wv::tid() >> 6; w < Wl; w += SCANB_THREADS / 64u) {
+        const u32 c = w * 64u + lane, m = c < N ? s.cmap[c] : 0u;
+        for (u32 r = 0; r < s.n_sc; ++r) {
+            const u64 word = wv::ballot(c < N && ((s.a.sc[(size_t)r * Wn + (m >> 6)] >> (m & 63)) & 1ull) != 0);
+            if (lane == 0) rows[(size_t)r * Wl + w] = word;
+        }
+    }
+}
+// SCAN_CM: the compact instance — N is the union's node count; the LDS rows, the matrices, the class rows' bits and the key's low 12 bits
+// carry the compact index, what leaves the kernel the node behind it (`real`, in registers for the stretch); false: today's code
+template <int SCAN_NQ, bool SCAN_CM = false>
 WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
     const R6Args& a = s.a;
-    const u32 tid = wv::tid(), lane = wv::lane(), N = a.n_nodes, Wn = a.n_words;
+    const u32 tid = wv::tid(), lane = wv::lane(), N = SCAN_CM ? s.n_c : a.n_nodes, Wn = a.n_words;
+    const u32 Wl = SCAN_CM ? (N + 63u) / 64u : Wn;   // words of a class row in LDS
     unsigned char* l = reinterpret_cast<unsigned char*>(wv::lds());
     i64* cpu = reinterpret_cast<i64*>(l);
     i64* mem = cpu + N;
@@ -403,16 +427,25 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
     int32_t* lastc = reinterpret_cast<int32_t*>(tot + N);
     u32* hm = reinterpret_cast<u32*>(l + (((size_t)N * 24 + 15) & ~(size_t)15));
     u32* em = hm + (size_t)s.n_svc * N;
-    u64* scl = reinterpret_cast<u64*>(em + (size_t)s.n_svc * N);                                   // [n_sc][Wn] the static class rows
-    u64* red = scl + (size_t)s.n_sc * Wn;                                                            // [3][SCAN_B] the argmins, three sets in rotation
+    u64* scl = reinterpret_cast<u64*>(em + (size_t)s.n_svc * N);                                   // [n_sc][Wl] the static class rows
+    u64* red = scl + (size_t)s.n_sc * Wl;                                                            // [3][SCAN_B] the argmins, three sets in rotation
     u64* wlive = red + 3 * SCAN_B;                                                                   // [SCAN_W / 64] the window's queue: tasks to be looked at
     u32* wrec = reinterpret_cast<u32*>(l + ((reinterpret_cast<unsigned char*>(wlive + SCAN_W / 64) - l + 15) & ~(size_t)15));   // [SCAN_W][16] the window's task records
     u32* wtm = wrec + SCAN_W * 16;                                                                   // [SCAN_W] ... and descriptor ids
     u32* dtab = wtm + SCAN_W;                                                                        // [SCAN_DT] descriptors found unplaceable (id + 1; 0: free)
     if (a.blk->error != ERR_NONE) return;
-    for (u32 n = tid; n < N; n += SCANB_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
+    if (!SCAN_CM)
+        for (u32 n = tid; n < N; n += SCANB_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
+    else
+        for (u32 c = tid; c < N; c += SCANB_THREADS) {
+            const u32 m = s.cmap[c];
+            cpu[c] = a.cpu[m]; mem[c] = a.mem[m]; tot[c] = a.total[m]; lastc[c] = a.last[m];
+        }
     for (u32 x = tid; x < s.n_svc * N; x += SCANB_THREADS) { hm[x] = s.hmat[x]; em[x] = s.emat[x]; }
-    for (u32 x = tid; x < s.n_sc * Wn; x += SCANB_THREADS) scl[x] = a.sc[x];
+    if (!SCAN_CM)
+        for (u32 x = tid; x < s.n_sc * Wn; x += SCANB_THREADS) scl[x] = a.sc[x];
+    else
+        scanb_rows_c(s, scl);
     for (u32 x = tid; x < SCAN_DT; x += SCANB_THREADS) dtab[x] = 0;
     if (tid < 3 * SCAN_B) red[tid] = KEY_NONE;
     u32 nc = a.ctl->ncommit, ni = a.ctl->ninf;
@@ -433,11 +466,13 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
     window_load(s.j0);
     // this thread's nodes (a node beyond the last one tests no class bit: it is never a candidate)
     u32 nn[SCAN_NQ], cbit[SCAN_NQ];
+    u32 real[SCAN_CM ? SCAN_NQ : 1];   // SCAN_CM: the nodes behind this thread's rows
     WV_UNROLL
     for (int q = 0; q < SCAN_NQ; ++q) {
         const u32 n = tid + (u32)q * SCANB_THREADS;
         nn[q] = min(n, N - 1u);
         cbit[q] = n < N ? 1u << (n & 31u) : 0u;
+        if (SCAN_CM) real[q] = n < N ? s.cmap[n] : 0u;
     }
     const u32* scl32 = reinterpret_cast<const u32*>(scl);
     u32 slot = 0, skipped = 0, batches = 0, over = 0;
@@ -521,7 +556,7 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
                     ecpu[b] = (fl & RT_RES) ? rcpu[b] : INT64_MIN;
                     emem[b] = (fl & RT_RES) ? rmem[b] : INT64_MIN;
                     emax[b] = (fl & RT_MAXREP) ? (rmax[b] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)rmax[b]) : 0xFFFFFFFFu;
-                    scoff[b] = wv::readfirstlane(rsc[b]) * Wn * 2u;
+                    scoff[b] = wv::readfirstlane(rsc[b]) * Wl * 2u;
                     svoff[b] = wv::readfirstlane(rsvc[b]) * N;
                 }
                 // ---- every thread: the best of its own nodes, for each of the batch's tasks. First every word the evaluations read — a task's
@@ -617,8 +652,15 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
                     WV_UNROLL
                     for (int b = 0; b < SCAN_B; ++b) {
                         if (!mine[b]) continue;
-                        const u32 nd = gn[b], w = nd >> 6, tb = base + ib[b];
-                        const u64 bit = 1ull << (nd & 63);
+                        const u32 nd = gn[b], tb = base + ib[b];
+                        u32 m = nd;   // the node behind the row
+                        if (SCAN_CM) {
+                            WV_UNROLL
+                            for (int q = 0; q < SCAN_NQ; ++q)
+                                if (tid + (u32)q * SCANB_THREADS == nd) m = real[q];
+                        }
+                        const u32 w = m >> 6;
+                        const u64 bit = 1ull << (m & 63);
                         cpu[nd] -= rcpu[b];
                         mem[nd] -= rmem[b];
                         if (!(rfl[b] & RT_UNCOUNTED)) {
@@ -629,7 +671,7 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
                             hm[(size_t)rsvc[b] * N + nd] = hi;
                             if (entry == LIST_EMPTY) {
                                 wv::g_or64(a.X + (size_t)rsvc[b] * a.xs + w, bit);
-                                a.list_node[rslot[b]] = nd;
+                                a.list_node[rslot[b]] = m;
                                 a.list_svc[rslot[b]] = 1;
                                 a.list_fail[rslot[b]] = 0;
                                 em[(size_t)rsvc[b] * N + nd] = rslot[b];
@@ -637,11 +679,11 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
                                 a.list_svc[entry] = hi & 0xFFFFFFu;
                         }
                         const int32_t prev = lastc[nd];
-                        a.log_node[ncb[b]] = nd;
+                        a.log_node[ncb[b]] = m;
                         a.log_task[ncb[b]] = tb;
                         a.log_prev[ncb[b]] = prev;
                         lastc[nd] = (int32_t)ncb[b];
-                        a.out_node[tb] = (int32_t)nd;
+                        a.out_node[tb] = (int32_t)m;
                     }
                 }
                 SCAN_TICK(4);
@@ -677,7 +719,15 @@ WV_KERNEL(SCANB_THREADS) void k_scanb(ScanArgs s) {
     }
     if (over) a.blk->error = ERR_LEVEL_RANGE;
     wv::barrier();
-    for (u32 n = tid; n < N; n += SCANB_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    if (!SCAN_CM)
+        for (u32 n = tid; n < N; n += SCANB_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    else {   // the union's nodes only: no other node was read, none is written
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 c = tid + (u32)q * SCANB_THREADS, m = real[q];
+            if (c < N) { a.cpu[m] = cpu[c]; a.mem[m] = mem[c]; a.total[m] = tot[c]; a.last[m] = lastc[c]; }
+        }
+    }
     if (tid == 0) {
         a.ctl->ncommit = nc;
         a.ctl->ninf = ni;
