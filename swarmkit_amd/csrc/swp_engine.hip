@@ -1906,6 +1906,8 @@ struct R6Run {   // what a run decides once and its stretches share
     R6Shape shape;
     bool task_rows;
     uint32_t nrr, block;   // demand-class rows in the commit kernel's LDS; the largest block it holds next to them
+    uint32_t ring_block = 0;   // the block of a ring round (swp_rounds.hpp r6_ring); 0: this run has none
+    uint32_t largest() const { return std::max(block, ring_block); }   // what the buffers are sized for
     uint32_t wi = 0;       // resolver stretches launched so far (profiling slots)
     uint64_t rounds = 0;
 };
@@ -1914,6 +1916,7 @@ struct R6Stretch {   // one stretch [start, end) of k_resolve6's rounds: what it
     R6Args ra;
     RoundRules rules;   // pace, compact switch, scan hand-over
     Blk6 hb{};          // the control block as last read
+    uint32_t ring_rounds = 0;   // ring rounds enqueued (a round past the stretch's end included)
 };
 R6Words r6_words(const Blk6& hb) { return R6Words{hb.pos, hb.rounds, hb.cut_exhausted + hb.cut_window, hb.crounds, hb.reseats, hb.scan_skipped}; }
 
@@ -1931,6 +1934,11 @@ int r6_run_plan(swp_engine* e, swp_batch* b, R6Run* run) {
     run->block = r6_fit_block(run->shape.cap, [&](uint32_t bl) { return r6_commit_lds_size(Wn, bl, nrr, cpt_room, win); });
     if (r6_propose_lds_size(Wn) > R6_LDS_BUDGET || r6_commit_lds_size(Wn, run->block, nrr, false, win) > R6_LDS_BUDGET || Wn > 32768u)   // (half-word indices of 16 bits in the commit kernel's LDS)
         return e->fail(SWP_ERANGE, "node count %u exceeds the block resolver's LDS (shard the node set)", e->n_nodes);
+    // ring rounds: where the rule may ever say yes for this batch (a stretch asks it again, round by round) and the ring instance fits
+    if (r6_ring(run->knobs, !run->shape.runs, !b->csi_set.empty(), true, Wn, 0xFFFFFFFFu, run->block)) {
+        const uint32_t rb = r6_ring_block(run->knobs, run->shape.cap, r6_ring_block_max());
+        if (r6_commit_lds_ring_size(Wn, rb, nrr, R6_RING_TASKS, win) <= R6_LDS_BUDGET) run->ring_block = rb;
+    }
     return SWP_OK;
 }
 
@@ -1957,9 +1965,11 @@ int grow_events(swp_engine* e, std::vector<hipEvent_t>& pool, size_t n) {
 }
 
 // `chunk` rounds: in one piece, or streamed in pieces with a publish behind each (the last piece included: a stretch ends published)
-int launch_chunk(swp_engine* e, swp_batch* b, StreamRun* sx, const R6Args& ra, uint32_t chunk) {
+// (flat_block: the run's largest flat block — ring rounds keep the publishes' cadence in tasks, swp_rounds.hpp r6_ring_stream_every)
+int launch_chunk(swp_engine* e, swp_batch* b, StreamRun* sx, const R6Args& ra, uint32_t chunk, uint32_t flat_block) {
     for (uint32_t done = 0; done < chunk;) {
-        const uint32_t piece = sx ? std::min<uint32_t>(stream_rounds(sx), chunk - done) : chunk;
+        const uint32_t every = !sx ? 0u : ra.ring ? r6_ring_stream_every(stream_rounds(sx), flat_block, ra.block) : stream_rounds(sx);
+        const uint32_t piece = sx ? std::min<uint32_t>(every, chunk - done) : chunk;
         const hipError_t r = launch_r6_rounds(ra, piece, e->stream, e->device);
         if (r != hipSuccess) return e->fail(SWP_EHIP, "k_r6 round launch: %s", hipGetErrorString(r));
         done += piece;
@@ -2077,8 +2087,14 @@ void stretch_report(swp_batch* b, const R6Run& run, const R6Stretch& s) {
     }
 #endif
     if (hb.crounds) fprintf(stderr, "[swp] %u of the %u rounds with a compact index | of the cuts at an exhausted list: %u full lists, %u lists in compact positions, %u lists of one entry\n", hb.crounds, hb.rounds, hb.dbg_cut[0], hb.dbg_cut[1], hb.dbg_cut[2]);
+    // (lists: what the stretch's last chunk of flat rounds would list, RoundRules::ext() as it stands at the end; the ring's details only
+    // where ring rounds were enqueued — rounds past the stretch's end, which are empty launches, included)
+    fprintf(stderr, "[swp] k_resolve6 blocks: flat %u, lists of %u | ring %s", run.block, s.rules.ext() ? (uint32_t)R6_LIST : 2u * R6_CAND, s.ring_rounds ? "on" : "off");
+    if (s.ring_rounds) fprintf(stderr, ": blocks of %u over a ring of %u tasks, lists of %u, %u rounds enqueued as ring rounds", run.ring_block, R6_RING_TASKS, R6_RING_LIST, s.ring_rounds);
+    fprintf(stderr, "\n");
+    // (the block: the ring's where ring rounds were enqueued — the line above says how many — the flat one otherwise)
     fprintf(stderr, "[swp] k_resolve6 tasks [%u, %u): %u rounds of %u (%.1f decided each) | cut by an exhausted list %u, a window that ran out %u, an exception-list task %u, an uncounted task %u | proposals with a second section %u\n", s.start, s.end,
-            hb.rounds, run.block, (double)(s.end - s.start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted, hb.dbg_lv2);
+            hb.rounds, s.ring_rounds ? run.ring_block : run.block, (double)(s.end - s.start) / std::max<uint32_t>(hb.rounds, 1), hb.cut_exhausted, hb.cut_window, hb.cut_exception, hb.cut_uncounted, hb.dbg_lv2);
     r6_report(hb, false);
 }
 
@@ -2093,8 +2109,17 @@ RoundRules stretch_rules(swp_engine* e, swp_batch* b, const R6Run& run, const R6
     const bool scan_whole = N <= scan_max_nodes();
     const bool scan_ok = (scan_whole || run.knobs.scan_compact) && run.knobs.scan && b->csi_set.empty() && !b->wide_keys;
     const bool scan_fast = ra.n_rg == 0 && ra.csi_of == nullptr && scan_batched_fits(N, b->n_svc, b->n_sc);
-    return RoundRules{RoundPace(end - start, run.block, run.knobs.block_forced, start), CompactSwitch(cpt_allowed, run.knobs, e->r6_compact_hint),
-                      scan_whole ? ScanHandover(scan_ok, scan_fast) : ScanHandover::conditional(scan_ok, scan_max_nodes()), !run.shape.runs};
+    // (a stretch that may have ring rounds is paced with the ring block as its largest; its other rounds end at the flat block: RoundRules::block)
+    const bool may_ring = run.ring_block != 0 && r6_ring(run.knobs, !run.shape.runs, !b->csi_set.empty(), true, Wn, end - start, run.block);
+    RoundRules rules{RoundPace(end - start, may_ring ? run.ring_block : run.block, run.knobs.block_forced, start), CompactSwitch(cpt_allowed, run.knobs, e->r6_compact_hint),
+                     scan_whole ? ScanHandover(scan_ok, scan_fast) : ScanHandover::conditional(scan_ok, scan_max_nodes()), !run.shape.runs};
+    if (may_ring) {
+        rules.flat = run.block;
+        rules.ring_mounts = !b->csi_set.empty();
+        rules.n_words = Wn;
+        rules.ring_knobs = run.knobs;
+    }
+    return rules;
 }
 
 // On the stream: the stretch's position and end, the bitmaps built from the node rows as they are.
@@ -2103,7 +2128,8 @@ int stretch_begin(swp_engine* e, swp_batch* b, const R6Run& run, R6Stretch& s) {
     // lists of R6_LIST half-words, the entries behind a proposal's 32 (RoundRules::ext: only for full-size blocks of ordinary batches.
     // Wave 0 of every propose workgroup pays for listing them, and neither a batch of runs nor rounds that are cut after a few dozen
     // tasks get anything for it: service-major cfg3 and the churn rounds were slower with them)
-    HIPCHECK(e, b->d_ext.reserve((size_t)run.block * sizeof(R6PropExt)));
+    // (a ring round's records are the longer R6PropExtRing, in the same buffer: the _r instances read R6Args.ext so)
+    HIPCHECK(e, b->d_ext.reserve(std::max((size_t)run.block * sizeof(R6PropExt), (size_t)run.ring_block * sizeof(R6PropExtRing))));
     s.ra.ext = s.rules.ext() ? b->d_ext.as<R6PropExt>() : nullptr;
     s.ra.win = run.shape.win;
     if (run.prof) {
@@ -2122,7 +2148,7 @@ int stretch_begin(swp_engine* e, swp_batch* b, const R6Run& run, R6Stretch& s) {
 // own (the position lives in the control block); the host only learns every so many rounds how far it is, and asks the rules.
 int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_t end) {
     R6Args ra{};
-    if (int rc = r6_args_for(e, b, run.block, run.task_rows, run.knobs, &ra)) return rc;
+    if (int rc = r6_args_for(e, b, run.largest(), run.task_rows, run.knobs, &ra)) return rc;
     R6Stretch s{start, end, ra, stretch_rules(e, b, run, ra, start, end)};
     if (int rc = stretch_begin(e, b, run, s)) return rc;
     RoundPace& pace = s.rules.pace;
@@ -2130,11 +2156,14 @@ int run_stretch(swp_engine* e, swp_batch* b, R6Run& run, uint32_t start, uint32_
     const uint32_t dbg_bits = run.knobs.dbg;
     bool unread = false;   // a stretch went through k_scanb since the words were last read
     while (pace.pos < end) {
-        s.ra.block = pace.block;
+        const bool ring = s.rules.ring();   // (for the whole chunk: one that runs into the stretch's last flat block ends on ring rounds of fewer tasks)
+        s.ra.block = s.rules.block();
+        s.ra.ring = ring ? R6_RING_TASKS : 0u;
         s.ra.compact = s.rules.cpt.compact();
         s.ra.ext = s.rules.ext() ? b->d_ext.as<R6PropExt>() : nullptr;
-        s.ra.levels2 = r6_levels2(run.knobs, s.ra.ext != nullptr, s.ra.n_words, R6_LIST) ? 1u : 0u;
-        if (int rc = launch_chunk(e, b, run.sx, s.ra, pace.chunk)) return rc;
+        s.ra.levels2 = r6_levels2(run.knobs, s.ra.ext != nullptr, s.ra.n_words, ring ? R6_RING_LIST : (uint32_t)R6_LIST) ? 1u : 0u;
+        if (ring) s.ring_rounds += pace.chunk;
+        if (int rc = launch_chunk(e, b, run.sx, s.ra, pace.chunk, run.block)) return rc;
         if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
         unread = false;
         if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");

@@ -14,7 +14,9 @@ hipError_t ensure_big_lds(const void* fn, int device);
 struct R6Args;
 size_t r6_propose_lds_size(uint32_t n_words);
 size_t r6_commit_lds_size(uint32_t n_words, uint32_t block, uint32_t n_rr, bool compact = false, uint32_t win = 0);   // win: R6Args.win   // compact: with the room for a compact index (k_r6_compact)
-uint32_t r6_block_max();   // the largest block of a single engine ...
+size_t r6_commit_lds_ring_size(uint32_t n_words, uint32_t block, uint32_t n_rr, uint32_t ring, uint32_t win = 0);   // ... of a ring round (R6Args.ring)
+uint32_t r6_ring_block_max();   // the largest block of a ring round (R6_BMAX)
+uint32_t r6_block_max();   // the largest flat block of a single engine ...
 uint32_t r7_block_max();   // ... and of the node-range shards
 // Tasks per round of the block resolver unless SWP_R6_BLOCK says otherwise. A single engine: as many 64-task groups as the commit
 // kernel's LDS holds (windows of R6_WIN list entries a task: 1 408 tasks next to the TK row of 10 000 nodes); the shards, whose commit

@@ -9,6 +9,7 @@
 #define SWP_VOL_KERNELS
 #include "swp_resolve6.hpp"
 #include "swp_resolve7.hpp"
+#include "swp_rounds.hpp"
 #include "swp_fitpairs.hpp"
 #define SWP_ENF_KERNELS
 #include "swp_enforce.hpp"
@@ -17,9 +18,25 @@
 
 namespace swpdev {
 
+// the host rule's figures (swp_rounds.hpp knows no kernel header) are the kernels'
+static_assert(R6_RING_TASKS == R6_RING && R6_RING_LIST == R6_LIST_RING && R6_RING_BLOCK == R6_BMAX, "swp_rounds.hpp and swp_resolve6.hpp disagree on the ring");
+#if R6_RING_ON
+#define R6_COMMIT_RING_KERNEL k_r6_commit_r
+#define R6_PROPOSE_RING_KERNEL k_r6_propose_r
+#define R6_PROPOSE_SMALL_RING_KERNEL k_r6_propose_small_r
+#define R6_PROPOSE_TINY_RING_KERNEL k_r6_propose_tiny_r
+#else   // (never launched: launch_r6_rounds refuses R6Args.ring in a build without the ring)
+#define R6_COMMIT_RING_KERNEL k_r6_commit
+#define R6_PROPOSE_RING_KERNEL k_r6_propose
+#define R6_PROPOSE_SMALL_RING_KERNEL k_r6_propose_small
+#define R6_PROPOSE_TINY_RING_KERNEL k_r6_propose_tiny
+#endif
+
 size_t r6_propose_lds_size(uint32_t n_words) { return r6_propose_lds(n_words); }
 size_t r6_commit_lds_size(uint32_t n_words, uint32_t block, uint32_t n_rr, bool compact, uint32_t win) { return r6_commit_lds(n_words, block, n_rr, compact, win); }
-uint32_t r6_block_max() { return R6_BMAX; }
+size_t r6_commit_lds_ring_size(uint32_t n_words, uint32_t block, uint32_t n_rr, uint32_t ring, uint32_t win) { return r6_commit_lds_ring(n_words, block, n_rr, ring, win); }
+uint32_t r6_block_max() { return R6_FLAT_BMAX; }
+uint32_t r6_ring_block_max() { return R6_BMAX; }
 uint32_t r7_block_max() { return R7_BMAX; }
 
 // base / highest level, then level planes + demand-class rows from the node rows as they are
@@ -32,10 +49,14 @@ hipError_t launch_r6_build(const R6Args& a, hipStream_t s) {
 // `rounds` rounds of propose + commit; a round past the end of the stretch is a no-op
 hipError_t launch_r6_rounds(const R6Args& a, uint32_t rounds, hipStream_t s, int dev) {
     const bool cpt = a.compact != 0 && !a.csi_of;   // (a batch with cluster mounts has its own commit instance, without the index)
-    const size_t lp = r6_propose_lds(a.n_words), lc = r6_commit_lds(a.n_words, a.block, a.n_dc + a.n_dm, cpt, a.win);
+    // a ring round (R6Args.ring): the plain instance's only, with the long lists, and a block the kernels' arrays are sized for
+    if (a.ring && (!R6_RING_ON || cpt || a.csi_of || !a.ext || a.ring != R6_RING || a.block > R6_BMAX)) return hipErrorInvalidValue;
+    if (!a.ring && a.block > R6_FLAT_BMAX) return hipErrorInvalidValue;   // (the flat instances' twin count ends there)
+    const size_t lp = r6_propose_lds(a.n_words);
+    const size_t lc = a.ring ? r6_commit_lds_ring(a.n_words, a.block, a.n_dc + a.n_dm, a.ring, a.win) : r6_commit_lds(a.n_words, a.block, a.n_dc + a.n_dm, cpt, a.win);
     hipError_t r;
-    if (lp > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(cpt ? &k_r6_propose_c : &k_r6_propose), dev)) != hipSuccess) return r;
-    if (lc > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(cpt ? &k_r6_commit_c : a.csi_of ? &k_r6_commit_v : &k_r6_commit), dev)) != hipSuccess) return r;
+    if (lp > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(cpt ? &k_r6_propose_c : a.ring ? &R6_PROPOSE_RING_KERNEL : &k_r6_propose), dev)) != hipSuccess) return r;
+    if (lc > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(cpt ? &k_r6_commit_c : a.csi_of ? &k_r6_commit_v : a.ring ? &R6_COMMIT_RING_KERNEL : &k_r6_commit), dev)) != hipSuccess) return r;
     // compact == 2: k_r6_commit_c builds the next round's index at its end; a launch of k_r6_compact only in front of the chunk's first round
     // (the state may have moved since the last commit: a scan stretch, a rebuild). Task-rows mode builds the rows the index pass reads
     // at the START of a round: there the index keeps its own launch.
@@ -52,11 +73,16 @@ hipError_t launch_r6_rounds(const R6Args& a, uint32_t rounds, hipStream_t s, int
             hipLaunchKernelGGL(k_r6_commit_c, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, ac);
             continue;
         }
-        if (a.n_words <= R6_TINY_WORDS && a.block > 1024u) hipLaunchKernelGGL(k_r6_propose_tiny,   // (up to 1 024 workgroups of eight waves are resident together as they are)
+        if (a.ring) {   // the ring rounds' instances, chosen as the flat ones below
+            if (a.n_words <= R6_TINY_WORDS && a.block > 1024u) hipLaunchKernelGGL(R6_PROPOSE_TINY_RING_KERNEL, dim3(a.block), dim3(64 * R6_PW_TINY), lp, s, a);
+            else if (a.n_words <= R6_SMALL_WORDS) hipLaunchKernelGGL(R6_PROPOSE_SMALL_RING_KERNEL, dim3(a.block), dim3(64 * R6_PW), lp, s, a);
+            else hipLaunchKernelGGL(R6_PROPOSE_RING_KERNEL, dim3(a.block), dim3(64 * R6_PW), lp, s, a);
+        } else if (a.n_words <= R6_TINY_WORDS && a.block > 1024u) hipLaunchKernelGGL(k_r6_propose_tiny,   // (up to 1 024 workgroups of eight waves are resident together as they are)
              dim3(a.block), dim3(64 * R6_PW_TINY), lp, s, a);
         else if (a.n_words <= R6_SMALL_WORDS) hipLaunchKernelGGL(k_r6_propose_small, dim3(a.block), dim3(64 * R6_PW), lp, s, a);   // (LDS of 8 chunks: never beyond 48 KB)
         else hipLaunchKernelGGL(k_r6_propose, dim3(a.block), dim3(64 * R6_PW), lp, s, a);
         if (a.csi_of) hipLaunchKernelGGL(k_r6_commit_v, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, a);
+        else if (a.ring) hipLaunchKernelGGL(R6_COMMIT_RING_KERNEL, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, a);
         else hipLaunchKernelGGL(k_r6_commit, dim3(1), dim3(R6_COMMIT_THREADS), lc, s, a);
     }
     return hipGetLastError();

@@ -42,6 +42,8 @@
 #pragma once
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "swp_shard.hpp"
 #include "swp_types.hpp"
 #include "swp_volumes.hpp"
@@ -67,15 +69,27 @@ namespace swpdev {
 #ifndef R6_REACH
 #define R6_REACH(what, cond)     // tests/emu counts the paths of the matcher a run came across (a driver defines it in front of this header); nothing in the product
 #endif
-#define R6_BMAX 2048             // largest block of a single engine (waves 1..15 of the commit kernel apply its 64-task groups in turn)
+#ifndef R6_RING_ON
+#define R6_RING_ON 1             // the ring instance of the commit kernel and the long lists of its rounds (R6Args.ring); 0: compiled out (A/B builds — launch_r6_rounds
+                                 // then refuses R6Args.ring, so run them with SWP_R6_RING=0 — and tests/emu)
+#endif
+#ifndef R6_RING_REACH
+#define R6_RING_REACH(what, cond)   // tests/emu/emu_resolve6_ring.cpp counts the ring's own paths (R6RR_*); nothing in the product, nothing in the other drivers
+#endif
+#define R6_BMAX 2816             // largest block of a single engine (waves 1..15 of the commit kernel apply its 64-task groups in turn): a RING block
+                                 // (R6Args.ring, the _r instances of the kernels); a flat block, which lies in LDS as a whole, ends at R6_FLAT_BMAX
+#define R6_FLAT_BMAX 2048
+#define R6_RING 960              // tasks of the commit kernel's ring: one slot of 64 tasks for each of its fifteen helper waves
 #define R7_BMAX 1024             // ... of the node-range shards: one group per wave of their commit kernel
 #define R6_COMMIT_THREADS 1024
 #define R6_LIST 64               // half-words the propose kernels list at most: the first 2 * R6_CAND in the proposal, the others in its extension (R6PropExt)
+#define R6_LIST_RING 128         // ... in a ring round (R6Args.ring): a block of 2 816 picks is 88 half-words of one level's nodes
 #ifndef R6_WIN
 #define R6_WIN 16                // list entries of a task the commit kernel keeps in LDS: the first that are live when the task's group is staged
 #endif
 #define R6_NONE 0xFFFFFFFFu
 
+enum { R6RR_SKIPPED3, R6RR_WRAPPED_STAGE, R6RR_N };   // R6_RING_REACH: a staging that skipped >= 3 dead batches of sixteen; a stage() into a reused slot
 struct Blk6 {   // control block, global memory
     u32 pos, end;          // next undecided task, end of the stretch
     u32 base, maxrel;      // lowest task count among the valid nodes at build time; highest level above it so far
@@ -111,11 +125,17 @@ struct R6Prop {   // one task's proposal: the shard protocol's record (include/s
 };
 static_assert(sizeof(R6Prop) == 8 + 12 * R6_CAND + 24, "R6Prop layout");
 static_assert(2 * R6_CAND <= 64, "one lane per list entry");
-struct R6PropExt {   // entries 2 * R6_CAND .. R6_LIST - 1 of a task's list (R6Args.ext): read by k_r6_commit only, never sent between shards
+struct R6PropExt {   // entries 2 * R6_CAND .. R6_LIST - 1 of a task's list (R6Args.ext): read by the commit kernel only, never sent between shards
     unsigned short hw[R6_LIST - 2 * R6_CAND];
     u32 hb[R6_LIST - 2 * R6_CAND];
 };
-static_assert(R6_WIN >= 1 && R6_WIN <= 2 * R6_CAND && R6_LIST % 16 == 0 && (2 * R6_CAND) % 16 == 0, "the window staging reads 16 entries a batch");
+struct R6PropExtRing {   // ... of a RING round (R6Args.ring), entries up to R6_LIST_RING - 1: what R6Args.ext points to there, for the _r instances alone —
+                         // a flat round's records, and the flat instances' code, are what they were without a ring
+    unsigned short hw[R6_LIST_RING - 2 * R6_CAND];
+    u32 hb[R6_LIST_RING - 2 * R6_CAND];
+};
+static_assert(R6_WIN >= 1 && R6_WIN <= 2 * R6_CAND && R6_LIST % 16 == 0 && R6_LIST_RING % 16 == 0 && (2 * R6_CAND) % 16 == 0, "the window staging reads 16 entries a batch");
+static_assert(R6_LIST <= R6_LIST_RING && R6_RING == 15 * 64 && R6_BMAX % 64 == 0 && R6_FLAT_BMAX <= R6_BMAX, "ring geometry");
 
 struct R6Args {
     u32 n_nodes, n_words, xs, block;
@@ -189,6 +209,7 @@ struct R6Args {
     // round parity, right behind its proposals — they travel with them); nullptr: no volumes in the batch
     struct R7Trail* trail_out;   // = the slots of its R7Tail
     // [block] the list entries beyond the proposal's; nullptr: lists end with the proposal (the shard drivers: the record they exchange)
+    // (a ring round, `ring` below: [block] R6PropExtRing behind this pointer)
     R6PropExt* ext;
     u32 win;                 // list entries a task in the commit kernel's LDS (r6_win_of: 0 = R6_WIN); the launch sizes the LDS by it
     u32 no_runs;             // != 0: the batch has no run of >= 8 consecutive identical tasks (counted when it is built): the matcher leaves the
@@ -196,6 +217,10 @@ struct R6Args {
                              // 4 650 of a round's 160 k cycles)
     u32 levels2;             // != 0: a complete list goes on with a SECOND SECTION, the task's candidates one level up that lie in front of the first
                              // section (r6_propose_t, "the second section"); 0: lists of one level. Honoured by the instances without a compact index
+    u32 ring;                // != 0: a RING round (k_r6_commit_r; the host's rule: swp_rounds.hpp r6_ring). The commit kernel keeps the pick slots and the
+                             // windows of `ring` tasks (R6_RING) instead of the block's: group g lives in slot g % 15, the slot of the helper that
+                             // stages and applies it, so `block` may exceed what LDS holds; the propose kernels list up to R6_LIST_RING half-words.
+                             // 0: the whole block in LDS, lists of R6_LIST
 };
 struct R7Args;   // swp_resolve7.hpp: what a shard's commit kernel knows of the other shards
 #define R7_FOLDS_IN_FLIGHT 4u   // waves that fold at the same time (the R7 staging below); SWP_DBG bits 8-11 override it for A/B runs (tools/gpu_r5_foldwin.sh)
@@ -233,6 +258,12 @@ inline __host__ __device__ u32 r6_tk_words(u32 n_words) { return n_words + n_wor
 inline __host__ __device__ u32 r6_win_of(u32 win) { return win == 0 ? (u32)R6_WIN : win < 2u * R6_CAND ? win : 2u * R6_CAND; }
 inline __host__ __device__ size_t r6_commit_lds(u32 n_words, u32 block, u32 n_rr, bool compact = false, u32 win = 0) {
     return (size_t)((compact ? r6_tk_words(n_words) : n_words) + n_rr) * 8 + (size_t)block * (16 + r6_win_of(win) * 6) + 192;
+}
+// ... of the ring instance (R6Args.ring): the TK row still covers the block (it is per node), picks and windows are the ring's, and
+// staged[] is one flag per group of the BLOCK — the flat header's 32 flags are not enough — behind the 16 scalars
+inline __host__ __device__ u32 r6_ring_flags(u32 block) { return ((block + 63u) / 64u + 15u) / 16u * 16u; }
+inline __host__ __device__ size_t r6_commit_lds_ring(u32 n_words, u32 block, u32 n_rr, u32 ring, u32 win = 0) {
+    return (size_t)(n_words + n_rr) * 8 + (size_t)ring * (16 + r6_win_of(win) * 6) + 64 + (size_t)r6_ring_flags(block) * 4;
 }
 
 #ifdef SWP_R6_KERNELS   // the kernels: swp_resolve6.hip and the emulation harness only (the engine TU shares the argument records)
@@ -480,7 +511,9 @@ WV_KERNEL(1024) void k_r6_compact(R6Args a) {
 // ---- propose: one workgroup of R6_PW waves per task of the block -----------------------------------------------------------
 // The waves split the task's node words (wave v owns the chunks of 64 words k = v, v + R6_PW, ...): the passes are latency-bound,
 // so more waves per task is what shortens them. A pass ends with one barrier (has any wave a candidate left?).
-template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(const R6Args& a) {
+// (TWB: the largest block the instance's twin count covers — R6_FLAT_BMAX in the instances of the flat rounds, which are the code they
+// were before there was a ring; R6_BMAX in the _r instances, which the ring rounds launch)
+template <int UN, bool CPT = false, u32 PW = R6_PW, u32 TWB = R6_FLAT_BMAX> WV_DEV void r6_propose_t(const R6Args& a) {
     const u32 lane = wv::lane(), wave = wv::wave();
     const u32 t = wv::uload(&a.blk->pos) + wv::block();
     if (t >= wv::uload(&a.blk->end) || wv::uload(&a.blk->error) != ERR_NONE) return;   // (an error stops the rounds until the host has seen it)
@@ -519,12 +552,12 @@ template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(con
     // candidates of the level are gone whatever the other tasks did. Its list starts behind them (below): a block of one service's
     // tasks then walks 32 half-words PER TASK into the level instead of sharing one window of 32. The ids are requested here and
     // counted behind the pass.
-    u32 tw_id[(R6_BMAX + 64 * PW - 1) / (64 * PW)], tw_mine = 0;
+    u32 tw_id[(TWB + 64 * PW - 1) / (64 * PW)], tw_mine = 0;
     const u32 tw_pos = wv::uload(&a.blk->pos);
     if (a.tmpl) {
         tw_mine = wv::uload(a.tmpl + t);
         WV_UNROLL
-        for (u32 q = 0; q < (R6_BMAX + 64 * PW - 1) / (64 * PW); ++q) {
+        for (u32 q = 0; q < (TWB + 64 * PW - 1) / (64 * PW); ++q) {
             const u32 u = tw_pos + (q * PW + wave) * 64 + lane;
             tw_id[q] = u < t ? a.tmpl[u] : R6_NONE;
         }
@@ -595,7 +628,7 @@ template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(con
     u32 tw_cnt = 0;
     if (a.tmpl) {
         WV_UNROLL
-        for (u32 q = 0; q < (R6_BMAX + 64 * PW - 1) / (64 * PW); ++q) tw_cnt += (u32)wv::popc64(wv::ballot(tw_id[q] == tw_mine && tw_pos + (q * PW + wave) * 64 + lane < t));
+        for (u32 q = 0; q < (TWB + 64 * PW - 1) / (64 * PW); ++q) tw_cnt += (u32)wv::popc64(wv::ballot(tw_id[q] == tw_mine && tw_pos + (q * PW + wave) * 64 + lane < t));
     }
     if (lane == 0) {
         flag[wave] = best;
@@ -632,8 +665,11 @@ template <int UN, bool CPT = false, u32 PW = R6_PW> WV_DEV void r6_propose_t(con
     R6Prop* out = a.prop + wv::block();
     // its first non-empty half-words, in node order (what the matcher walks: a word that is half empty does not cost a list entry):
     // 64 words a step, a lane's place in the list = the non-empty half-words in front of it (two ballots)
-    R6PropExt* ext = a.ext ? a.ext + wv::block() : nullptr;
-    const u32 lmax = ext ? (u32)R6_LIST : 2u * R6_CAND;
+    // (an _r instance runs ring rounds only — launch_r6_rounds — and a ring round has an extension: its records are R6PropExtRing)
+    constexpr bool RINGP = R6_RING_ON && TWB > R6_FLAT_BMAX;
+    using Ext = typename std::conditional<RINGP, R6PropExtRing, R6PropExt>::type;
+    Ext* ext = a.ext ? reinterpret_cast<Ext*>(a.ext) + wv::block() : nullptr;
+    const u32 lmax = ext ? (RINGP ? (u32)R6_LIST_RING : (u32)R6_LIST) : 2u * R6_CAND;
     u32 cnt = 0, more = 0;
     u32 skip = twins, last_hw = 0, last_hb = 0;   // candidates still to pass over; the last non-empty half-word passed over
     u32 h0 = R6_NONE;   // the half-word of the level's first candidate, the twins' share included (the second section ends in front of its word)
@@ -801,6 +837,15 @@ WV_KERNEL(64 * R6_PW) void k_r6_propose_small(R6Args a) { r6_propose_t<1>(a); } 
 // n_words <= R6_TINY_WORDS only: four waves a task, each with one chunk — half the threads, so that the workgroups of a block of 1 408
 // are all resident at once (8 to a CU); at 157 node words three of eight waves had a word at all
 WV_KERNEL(64 * R6_PW_TINY) void k_r6_propose_tiny(R6Args a) { r6_propose_t<1, false, R6_PW_TINY>(a); }
+#if R6_RING_ON
+// ... the instances of the ring rounds (R6Args.ring): a twin count over blocks of up to R6_BMAX tasks, lists of up to R6_LIST_RING half-words
+WV_KERNEL(64 * R6_PW) void k_r6_propose_r(R6Args a) {
+    if (a.n_words <= R6_SMALL_WORDS) r6_propose_t<1, false, R6_PW, R6_BMAX>(a);
+    else r6_propose_t<R6_UNROLL, false, R6_PW, R6_BMAX>(a);
+}
+WV_KERNEL(64 * R6_PW) void k_r6_propose_small_r(R6Args a) { r6_propose_t<1, false, R6_PW, R6_BMAX>(a); }
+WV_KERNEL(64 * R6_PW_TINY) void k_r6_propose_tiny_r(R6Args a) { r6_propose_t<1, false, R6_PW_TINY, R6_BMAX>(a); }
+#endif
 // ... the instances that honour a round's compact index (launched behind k_r6_compact only)
 WV_KERNEL(64 * R6_PW) void k_r6_propose_c(R6Args a) {
     if (a.n_words <= R6_SMALL_WORDS) r6_propose_t<1, true>(a);
@@ -825,7 +870,10 @@ WV_DEV u32 r6_first_above(const i64* thr, u32 n, i64 q) {
 // (R7: the instance of the node-range shards, swp_resolve7.hpp — the same kernel on every shard: a thread FOLDS the proposals all shards
 // made for its task into one list in global node order while it stages it, wave 0 matches the block exactly as below — every shard
 // computes the same picks —, and a pick is applied by the shard that owns its node. m7 / my: the other shards' proposals, this shard's number.)
-template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6Args& a, const R7Args* m7 = nullptr, u32 my = 0) {
+// (RING: the ring instance, k_r6_commit_r — R6Args.ring != 0, no compact index, no cluster mounts, no runs-by-rank path. Pick slots and
+// windows are indexed by task % ring with `ring` as the row stride: RS below. Every other instance has RS == a.block and slot == task.)
+template <bool CPT, bool CSI, bool R7 = false, bool RING = false> WV_DEV void r6_commit_t(const R6Args& a, const R7Args* m7 = nullptr, u32 my = 0) {
+    static_assert(!RING || (!CPT && !CSI && !R7), "the ring is the plain instance's");
     const u32 tid = wv::tid(), lane = wv::lane();
     const u32 pos = a.blk->pos, end = a.blk->end;
     if (pos >= end || a.blk->error != ERR_NONE) return;   // a level beyond the planes: the proposals of this round were not written
@@ -841,11 +889,27 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     const u32 rnd = a.blk->rounds;   // (R7: the same on every shard — the parity of the trailer slots)
     u64* tk = wv::lds();                                         // [tkw] addresses taken by this block so far
     i64* thr = reinterpret_cast<i64*>(tk + tkw);                 // [n_rr] the demand-class thresholds
-    u32* pk_node = reinterpret_cast<u32*>(thr + n_rr);           // [block] node, R6_NONE = no suitable node
-    u32* pk_idx = pk_node + a.block;                             // [block] commit index / index among the unplaceable tasks
-    u32* pk_aux = pk_idx + a.block;                              // [block] exception-list entry (LIST_EMPTY: plain node) / commits before an unplaceable task
-    u32* sh = pk_aux + a.block;                                  // [0] accepted, [1] ncommit, [2] ninf, [3] tasks decided so far, [4] the matching is over
-    u32* staged = sh + 16;                                       // [R6_BMAX / 64] group g's lists are in LDS
+    // RING — the slot of 64 tasks that group g uses is g % 15's, the slot of helper g % 15. Reuse is safe, writer by writer:
+    //   * L_hw / L_hb / L_cur of slot s: written by the prologue (waves 0 and 1, groups 0 and 1 into slots 0 and 1, in front of their publish
+    //     of staged[0 / 1]) and by helper s alone, in its stage() and its cursor loop. A helper takes its groups g, g + 15, ... in order and
+    //     stages group g + 15 at the top of its loop, BEHIND its apply of group g; it applied g behind the matcher's publish of g's picks
+    //     (sh[3] >= the group's end). The matcher reads a slot only between its acquire of staged[g] and its publish of group g's picks —
+    //     its ah / ab registers live inside one group, and the release of that publish waits for every LDS read it has in flight — so it
+    //     is done with slot s for group g before helper s writes it for g + 15, and reads it for g + 15 only behind the acquire of
+    //     staged[g + 15], which helper s publishes behind its last stage() of that group.
+    //   * pk_node / pk_idx / pk_aux of slot s: written by the matcher for group g in front of its publish of g's picks, read by helper s in
+    //     its apply of g; the matcher writes them for g + 15 behind its acquire of staged[g + 15], which helper s published behind that
+    //     apply. The runs-by-rank path, whose scratch is a group's pick slots, is off in this instance.
+    //   * a block cut inside group g: helper g % 15 leaves its loop behind its apply; nobody stages a later group (a helper that finds
+    //     the matching over leaves without a publish), and the matcher's loop has ended.
+    // The TK row is per node, not per task: it holds every pick of the block, and windows are staged against it as ever.
+    const u32 RS = RING ? a.ring : a.block;                      // row stride of the pick and window arrays
+    u32* pk_node = reinterpret_cast<u32*>(thr + n_rr);           // [RS] node, R6_NONE = no suitable node
+    u32* pk_idx = pk_node + RS;                                  // [RS] commit index / index among the unplaceable tasks
+    u32* pk_aux = pk_idx + RS;                                   // [RS] exception-list entry (LIST_EMPTY: plain node) / commits before an unplaceable task
+    u32* sh = pk_aux + RS;                                       // [0] accepted, [1] ncommit, [2] ninf, [3] tasks decided so far, [4] the matching is over
+    u32* staged = sh + 16;                                       // [R6_FLAT_BMAX / 64; RING: r6_ring_flags(block)] group g's lists are in LDS
+    const u32 n_flags = RING ? r6_ring_flags(a.block) : 32u;
     // The lists in LDS, LW entries a task. R7: the whole folded list, staged by the prologue. Otherwise a WINDOW: the first `win` entries
     // that are live when the task's group is staged — groups 0 and 1 by the prologue (nothing is taken yet: the list's first entries),
     // group g >= 2 by the wave that will apply it, against the TK row once the matcher has published the picks of group g - 2. Taken
@@ -857,16 +921,16 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     constexpr u32 LMAX = 2u * R6_CAND;
     const u32 LW = R7 ? LMAX : r6_win_of(a.win);   // rows of the two arrays
     const u32 win = (R7 || !((a.dbg >> 12) & 31u)) ? LW : min((a.dbg >> 12) & 31u, LW);   // (dbg bits 12-16: a shorter window, tests)
-    u32* L_hb = sh + 48;                                         // [LW][block] entry-major: lane i of the matcher reads
-    u32* L_cur = L_hb + (size_t)LW * a.block;                    // ... entry k of task i at [k * block + i] (no bank conflicts); [block] a lower bound of every task's cursor: the entries in front of it are dead
+    u32* L_hb = sh + 16 + n_flags;                               // [LW][RS] entry-major: lane i of the matcher reads
+    u32* L_cur = L_hb + (size_t)LW * RS;                         // ... entry k of the task in slot i at [k * RS + i] (no bank conflicts); [RS] a lower bound of every task's cursor: the entries in front of it are dead
                                                                  // (not R7: | entries in the window << 8 | R6C_LEFT | the head's bits, R6C_*)
-    unsigned short* L_hw = reinterpret_cast<unsigned short*>(L_cur + a.block);   // [LW][block] the half-word indices, 16 bits each (the engine refuses node sets beyond 2^21 nodes)
+    unsigned short* L_hw = reinterpret_cast<unsigned short*>(L_cur + RS);   // [LW][RS] the half-word indices, 16 bits each (the engine refuses node sets beyond 2^21 nodes)
     u32* H_level = reinterpret_cast<u32*>(L_hw + (size_t)LW * a.block);   // R7 only: [block] the folded record's level ...
     u32* H_meta = H_level + a.block;                                       // ... and its list length | R7M_* flags
-    for (u32 j = tid; j < a.block; j += R6_COMMIT_THREADS) L_cur[j] = 0;
+    for (u32 j = tid; j < RS; j += R6_COMMIT_THREADS) L_cur[j] = 0;
     for (u32 w = tid; w < (R7 ? tkw : Wn + VW); w += R6_COMMIT_THREADS) tk[w] = 0;
     for (u32 c = tid; c < n_rr; c += R6_COMMIT_THREADS) thr[c] = a.thr[c];
-    if (tid < 32) staged[tid] = 0;
+    if (tid < n_flags) staged[tid] = 0;
     // Wave v >= 1 applies the picks of the block's groups v - 1, v + 14, ... (group g: tasks 64 g ...) as soon as wave 0 has matched the
     // group, while it matches the next ones; the first group's task records are requested now. (R7: a block has sixteen groups at most,
     // and the last one is applied by wave 0 behind its matching.)
@@ -880,7 +944,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
     }
     const bool prof = (a.dbg & 16u) != 0;
     const u64 t0 = prof ? wv::clock64() : 0;
-    const bool runs_on = !R7 && a.tmpl != nullptr && a.no_runs == 0;   // the runs-by-rank path below
+    const bool runs_on = !R7 && !RING && a.tmpl != nullptr && a.no_runs == 0;   // the runs-by-rank path below
     u64 exc0_lo = 0;      // thread 0: the exception-list candidate of the block's first task, the only one that may use its own
     u32 exc0_entry = 0;
     wv::barrier();
@@ -918,8 +982,8 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             WV_UNROLL
             for (int k = 0; k < (int)LMAX; ++k)
                 if ((u32)k < win) {   // (behind the list's end: index 0 — the seating step reads an entry's TK word before it knows whether the entry counts)
-                    L_hw[(size_t)k * a.block + tid] = (u32)k < cnt ? (unsigned short)((k & 1) ? vh[k >> 1] >> 16 : vh[k >> 1] & 0xFFFFu) : (unsigned short)0;
-                    L_hb[(size_t)k * a.block + tid] = vb[k];
+                    L_hw[(size_t)k * RS + tid] = (u32)k < cnt ? (unsigned short)((k & 1) ? vh[k >> 1] >> 16 : vh[k >> 1] & 0xFFFFu) : (unsigned short)0;
+                    L_hb[(size_t)k * RS + tid] = vb[k];
                 }
             L_cur[tid] = (cnt << 8) | ((lv != R6_NONE && (total > cnt || (nc >> 31))) ? R6C_LEFT : 0u) | r6_head_bits(lv, xh, fl);
             if (runs_on) pk_idx[tid] = tm;   // the task's descriptor id, in its own pick slot: nobody reads the slot before the group is matched
@@ -949,15 +1013,16 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             return Head{H_level[j], mt & 0xFFu, (mt & R7M_EXC) ? 0ull : KEY_NONE, ((mt & R7M_UNC) ? 1u : 0u) | ((mt & R7M_CSI) ? 2u : 0u)};
         };
         if (R7 && CSI && sh[12]) csi_seen = true;   // a reservation arrived from another shard only now: the proposals of tasks with mounts were made without it
-        for (u32 g0 = 0; g0 < n && !stop; g0 += 64) {
-            const u32 i = g0 + lane, glim = min(64u, n - g0);
+        u32 sg = 0;   // the group's slot: its first task's place in the pick and window arrays (RING: g0 % ring; g0 otherwise)
+        for (u32 g0 = 0; g0 < n && !stop; g0 += 64, sg = (RING && sg + 64u >= RS) ? 0u : sg + 64u) {
+            const u32 i = g0 + lane, glim = min(64u, n - g0), si = sg + lane;
             const bool have = i < n;
             const u64 tg0 = prof ? wv::clock64() : 0;
             while (wv::lds_poll32(staged + (g0 >> 6)) == 0) wv::spin_pause();   // (long there, but for the first groups of a block)
             const u64 tga = prof ? wv::clock64() : 0;
-            const u32 lcur = have ? L_cur[i] : 0u;   // (the group's applying wave has skipped the dead entries so far)
+            const u32 lcur = have ? L_cur[si] : 0u;   // (the group's applying wave has skipped the dead entries so far)
             // the task's descriptor id (a RUN of identical tasks: below) — in a register before the run path uses the group's pick slots as scratch
-            const u32 tmid = (runs_on && have) ? pk_idx[i] : 0u;
+            const u32 tmid = (runs_on && have) ? pk_idx[si] : 0u;
             if (prof) wv::keep(lcur ^ tmid);   // (the timer below: behind the wait for both)
             const u64 th0 = prof ? wv::clock64() : 0;
             // (a window may be empty — every entry was dead when it was staged — where the list is not: the task is still a plain one)
@@ -983,6 +1048,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             // words behind them, the seats are filled by selects: a step is two LDS round trips — one with R6_SEAT_AHEAD, below — and no divergent branch. An entry is
             // consumed while a seat is free; the first one that finds none stays for the next visit, and so do those behind it)
             const u32 li = have ? i : 0u;
+            const u32 ls = RING ? (have ? si : sg) : li;   // the lane's column of the window arrays (RING, a lane without a task: the group's first, never another group's slot)
             // R6_SEAT_AHEAD: the entries at the cursor (ah, ab) are requested whenever the cursor has a new value — behind the group's
             // L_cur word and at the end of every seating step — and not waited for: they are in their registers by the time the walk
             // stops, so a stop starts with the TK reads, issued right behind its flush (one LDS round trip of a lone wave among sixteen
@@ -1001,8 +1067,8 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 for (int q = 0; q < R6_SEAT; ++q) {
                     const u32 c = min(cur + (u32)q, win - 1u);
                     R6_REACH(R6R_CLAMPED, have && cur + (u32)q > win - 1u && cur < nent);
-                    ah[q] = L_hw[c * a.block + li];
-                    ab[q] = L_hb[c * a.block + li];
+                    ah[q] = L_hw[c * RS + ls];
+                    ab[q] = L_hb[c * RS + ls];
                 }
             };
             if (R6_SEAT_AHEAD) ahead();
@@ -1062,7 +1128,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             u32 fdone = 0;   // lanes [0, fdone) have their picks from the run path
             u32 fr_w = 0, fr_b = 0;
             if constexpr (!R7) {
-                if (runs_on && g0 + 64u <= a.block) {   // (the scratch below: 64 pick slots from g0 on)
+                if (!RING && runs_on && g0 + 64u <= a.block) {   // (the scratch below: 64 pick slots from g0 on)
                     const bool simple = have && plain && !(tflags & 3u);
                     const u64 ns = ~wv::ballot(simple);
                     const u32 nsimple = min(glim, ns ? (u32)wv::ffs64(ns) : 64u);
@@ -1220,13 +1286,13 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
             const u64 mc = m_plain & below & lanes, mi = m_inf & below & lanes;
             if (lane < cut && have) {
                 if (plain) {
-                    pk_node[i] = m_pick;
-                    pk_idx[i] = nc + wv::mbcnt(mc);
-                    pk_aux[i] = LIST_EMPTY;
+                    pk_node[si] = m_pick;
+                    pk_idx[si] = nc + wv::mbcnt(mc);
+                    pk_aux[si] = LIST_EMPTY;
                 } else {   // no suitable node: final whatever the earlier tasks of the block did (feasibility only shrinks)
-                    pk_node[i] = R6_NONE;
-                    pk_idx[i] = ni + wv::mbcnt(mi);
-                    pk_aux[i] = nc + wv::mbcnt(mc);
+                    pk_node[si] = R6_NONE;
+                    pk_idx[si] = ni + wv::mbcnt(mi);
+                    pk_aux[si] = nc + wv::mbcnt(mc);
                 }
             }
             nc += (u32)wv::popc64(mc);
@@ -1272,14 +1338,16 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 a.blk->cyc_s[2] += (u32)(cy_s2 >> 6);
                 a.blk->dbg_walks += walks;
             }
-            R6_REACH(R6R_ROUND, r6_reach_round(a.blk, pos, acc, why, seat_steps, reseats, pk_node, pk_idx, pk_aux));   // (tests/emu: a round's outcome, for the comparison of two builds)
+            // (tests/emu: a round's outcome, for the comparison of two builds. Flat instances only: a ring's slots hold the picks of the last
+            // fifteen groups, not of [0, acc) — its driver checks outcomes, tests/emu/emu_resolve6_ring.cpp)
+            if constexpr (!RING) R6_REACH(R6R_ROUND, r6_reach_round(a.blk, pos, acc, why, seat_steps, reseats, pk_node, pk_idx, pk_aux));
         }
     }
     const u64 t2 = prof ? wv::clock64() : 0;
     const u32 base = a.blk->base;
     // NodeInfo.addTask for the accepted pick of block-local task `mine` (record r): the node rows, the bitmaps, the commit log
-    auto apply = [&](const u32 mine, const RTask& r) {
-        const u32 t = pos + mine, addr = pk_node[mine];
+    auto apply = [&](const u32 mine_task, const u32 mine, const RTask& r) {   // mine: the task's pick slot (== the task but in a ring)
+        const u32 t = pos + mine_task, addr = pk_node[mine];
         u32 nd = addr;
         if (CPT) nd = addr == R6_NONE ? R6_NONE : addr < 64u * VW ? a.cidx[addr] : addr - 64u * VW;   // a compact position, or a node behind them
         bool here = true;   // R7: the pick lies in this shard's range
@@ -1379,7 +1447,7 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 while (wv::lds_poll32(sh + 3) < need && wv::lds_poll32(sh + 4) == 0) wv::spin_pause();
         }
         const u32 acc_now = wv::readfirstlane(wv::lds_poll32(sh + 3));
-        if (mine0 < acc_now) apply(mine0, r0);
+        if (mine0 < acc_now) apply(mine0, mine0, r0);
     } else if (wave_ != 0) {
         // Helper h = wave - 1 takes the groups h, h + 15, ... in order: it stages the group's windows (g >= 2), moves the cursors over
         // entries that die while the matcher works on the group before, waits for the group's picks and applies them. Every wait polls
@@ -1389,15 +1457,17 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
         RTask r = r0;
         for (u32 g = wave_ - 1u; g * 64u < n; g += 15u) {
             const u32 g0 = g * 64u, j = g0 + lane, need = min(g0 + 64u, n);
+            const u32 sj = RING ? g0 % RS + lane : j;   // the task's slot
             const bool have = j < n;
             u32 cnt = 0, left = 0, hbits = 0;   // hbits: the head's bits of the task's L_cur word
             if (g >= 2u) {
                 const u32 jj = have ? j : 0u;
                 const R6Prop* q = a.prop + jj;
-                const R6PropExt* x = a.ext ? a.ext + jj : nullptr;
+                using Ext = typename std::conditional<RING, R6PropExtRing, R6PropExt>::type;   // (a ring round's records: written by the _r propose instances)
+                const Ext* x = a.ext ? reinterpret_cast<const Ext*>(a.ext) + jj : nullptr;
                 const u32 lv = q->level, nc = q->n_cand;
                 hbits = r6_head_bits(lv, q->exc_hi, q->flags);
-                if (runs_on && have) pk_idx[j] = a.tmpl[pos + j];   // (this wave applied the group fifteen in front of this one before it came here: other slots)
+                if (runs_on && have) pk_idx[sj] = a.tmpl[pos + j];   // (this wave applied the group fifteen in front of this one before it came here: other slots)
                 const u32 total = (have && lv != R6_NONE) ? (nc & 0x7FFFFFFFu) : 0u;   // (beyond 2 * R6_CAND only with an extension)
                 u32 at = 0;   // the entries in front of it are dead (whole batches of sixteen)
                 // The window from the TK row as it is: sixteen entries of the list at a time through registers, from `at` on, the live ones
@@ -1427,8 +1497,8 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                             if (p + (u32)k < total && (hbv[k] & ~tkv[k])) {
                                 any = true;
                                 if (cnt < win) {
-                                    L_hw[(size_t)cnt * a.block + j] = (unsigned short)hwv[k];
-                                    L_hb[(size_t)cnt * a.block + j] = hbv[k];
+                                    L_hw[(size_t)cnt * RS + sj] = (unsigned short)hwv[k];
+                                    L_hb[(size_t)cnt * RS + sj] = hbv[k];
                                     ++cnt;
                                 } else
                                     left = 1;
@@ -1439,8 +1509,12 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                     }
                     if (p < total) left = 1;
                     if (have) {
-                        for (u32 k = cnt; k < win; ++k) L_hw[(size_t)k * a.block + j] = 0;   // (as the prologue's: a valid TK word behind every entry the seating step may read)
-                        L_cur[j] = (cnt << 8) | (left << 16) | hbits;
+                        for (u32 k = cnt; k < win; ++k) L_hw[(size_t)k * RS + sj] = 0;   // (as the prologue's: a valid TK word behind every entry the seating step may read)
+                        L_cur[sj] = (cnt << 8) | (left << 16) | hbits;
+                    }
+                    if constexpr (RING) {
+                        R6_RING_REACH(R6RR_SKIPPED3, have && at >= 48u);
+                        R6_RING_REACH(R6RR_WRAPPED_STAGE, lane == 0 && g >= 15u);
                     }
                 };
                 // Taken nodes stay taken, so a window staged against an older TK row holds nothing wrong, only entries that may have died
@@ -1488,15 +1562,15 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
                 if (acc >= need || over) break;
                 if (g >= 2u && have && acc < g0) {   // (the matcher reads the cursor when it starts on the group; a later value is lost, no harm)
                     for (int q = 0; q < 4 && cur < cnt; ++q) {
-                        if (L_hb[(size_t)cur * a.block + j] & ~tk32[L_hw[(size_t)cur * a.block + j]]) break;
+                        if (L_hb[(size_t)cur * RS + sj] & ~tk32[L_hw[(size_t)cur * RS + sj]]) break;
                         ++cur;
                     }
-                    L_cur[j] = cur | (cnt << 8) | (left << 16) | hbits;
+                    L_cur[sj] = cur | (cnt << 8) | (left << 16) | hbits;
                 }
                 wv::spin_pause();
             }
             const u32 acc_now = wv::readfirstlane(wv::lds_poll32(sh + 3));
-            if (j < acc_now) apply(j, r);
+            if (j < acc_now) apply(j, sj, r);
             if (acc_now < need) break;
         }
     }
@@ -1515,6 +1589,9 @@ template <bool CPT, bool CSI, bool R7 = false> WV_DEV void r6_commit_t(const R6A
 WV_KERNEL(R6_COMMIT_THREADS) void k_r6_commit(R6Args a) { r6_commit_t<false, false>(a); }
 WV_KERNEL(R6_COMMIT_THREADS) void k_r6_commit_c(R6Args a) { r6_commit_t<true, false>(a); }   // ... with a compact index (launched behind k_r6_compact only)
 WV_KERNEL(R6_COMMIT_THREADS) void k_r6_commit_v(R6Args a) { r6_commit_t<false, true>(a); }   // ... for a batch with cluster mounts (R6Args.csi_of)
+#if R6_RING_ON
+WV_KERNEL(R6_COMMIT_THREADS) void k_r6_commit_r(R6Args a) { r6_commit_t<false, false, false, true>(a); }   // ... a ring round (R6Args.ring != 0): blocks beyond the LDS
+#endif
 
 #endif   // SWP_R6_KERNELS
 

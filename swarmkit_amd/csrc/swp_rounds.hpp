@@ -26,6 +26,7 @@ struct R6Knobs {
     bool scan_compact = true;    // SWP_SCAN_COMPACT=0: nor, on a cluster beyond the scan resolver's node count, one whose class rows' union would fit (no probe)
     bool twins = true;           // SWP_R6_TWINS=0: every list starts at its level's first candidate
     int levels = -1;             // SWP_R6_LEVELS: -1 unset and 1: lists over two levels where the rule allows them (r6_levels2), 0: never
+    int ring = -1;               // SWP_R6_RING: -1 unset (the rule decides: r6_ring), 0 never, 1 wherever the kernel allows it (tests, A/B runs)
 };
 inline int r6_knob01(const char* name) {   // -1 unset, else 0 / 1
     const char* env = getenv(name);
@@ -46,6 +47,7 @@ inline R6Knobs r6_knobs(uint32_t block_max, uint32_t default_cap) {
     k.scan_compact = r6_knob01("SWP_SCAN_COMPACT") != 0;
     k.twins = r6_knob01("SWP_R6_TWINS") != 0;
     k.levels = r6_knob01("SWP_R6_LEVELS");
+    k.ring = r6_knob01("SWP_R6_RING");
     return k;
 }
 
@@ -123,6 +125,36 @@ inline R6Shape r6_shape(const R6Knobs& k, uint32_t tasks_in_runs, uint32_t T) {
 // and only on node sets with more half-words than a list holds (`list` = R6_LIST): on a smaller one a complete list names the whole
 // level and what is in front of it is a handful of words. SWP_R6_LEVELS=0 switches it off; 1 is the default spelled out.
 inline bool r6_levels2(const R6Knobs& k, bool ext_on, uint32_t n_words, uint32_t list) { return k.levels != 0 && ext_on && 2u * (uint64_t)n_words > list; }
+
+// Ring rounds (swp_resolve6.hpp, R6Args.ring): the commit kernel keeps the windows and pick slots of fifteen 64-task groups, a slot per
+// helper wave reused for each of its groups in turn, so a block is no longer what the LDS holds; what ends a longer block is the list,
+// so a ring round's lists are R6_RING_LIST half-words long (a block of 2 816 picks is 88 half-words of one level's nodes). A round's
+// fixed cost — two launches, the commit kernel's prologue and tail, two gaps — is paid per ROUND: the headline goes from 73 rounds of
+// 1 408 to the model's 38 of 2 816 (tools/sim_window.py). On where ALL of these hold:
+//   * the long lists are (`ext_on`, RoundRules::ext(): no batch of runs, no shrunk block — hence no churn rounds, no compact index);
+//   * the batch has no cluster mounts (k_r6_commit_v has no ring) and the engine is single (the shard drivers never ask);
+//   * the node set has more half-words than a ring list holds: a small one cannot supply a long block's picks from one level;
+//   * the stretch has more tasks left than a flat block holds (`left` > `flat_block`): a ring round of fewer is a flat round with longer lists;
+//   * SWP_R6_BLOCK is not set: a forced block stays flat where it fits, as every test that pins a round count expects.
+// SWP_R6_RING=0: never. =1: wherever the kernel allows it (the first two lines), whatever the node set, the rest of the stretch and a
+// forced block — which is then the ring block (r6_ring_block).
+constexpr uint32_t R6_RING_TASKS = 960;     // = R6_RING: fifteen slots of 64 tasks
+constexpr uint32_t R6_RING_LIST = 128;      // = R6_LIST_RING
+constexpr uint32_t R6_RING_BLOCK = 2816;    // = R6_BMAX; 44 groups
+inline bool r6_ring(const R6Knobs& k, bool ext_on, bool mounts, bool single, uint32_t n_words, uint32_t left, uint32_t flat_block) {
+    if (k.ring == 0 || !ext_on || mounts || !single) return false;
+    if (k.ring > 0) return true;
+    return !k.block_forced && 2u * (uint64_t)n_words > R6_RING_LIST && left > flat_block;
+}
+// the block of a ring round: R6_RING_BLOCK, or what SWP_R6_BLOCK says (with SWP_R6_RING=1), in whole groups, within [64, ring_block_max]
+inline uint32_t r6_ring_block(const R6Knobs& k, uint32_t asked, uint32_t ring_block_max) {
+    const uint32_t b = k.block_forced ? asked : R6_RING_BLOCK;
+    return std::min<uint32_t>(ring_block_max / 64u * 64u, std::max<uint32_t>(64u, b / 64u * 64u));
+}
+// The streamed driver publishes every `every` rounds of a flat block; ring rounds keep that cadence in TASKS
+inline uint32_t r6_ring_stream_every(uint32_t every, uint32_t flat_block, uint32_t ring_block) {
+    return (uint32_t)std::max<uint64_t>(1u, (uint64_t)every * flat_block / std::max<uint32_t>(ring_block, 1u));
+}
 
 // The words of the control block the rules below read after a chunk of rounds or behind a scan stretch, all running totals: decided up
 // to pos; rounds that found work; rounds cut by an exhausted list or a window that ran out; rounds that had a compact index; matcher
@@ -233,7 +265,18 @@ struct RoundRules {
     CompactSwitch cpt;
     ScanHandover scan;
     bool ext_ok;   // lists beyond a proposal's 32 entries: not for a batch of runs, whose windows hold a whole proposal ...
-    bool ext() const { return ext_ok && pace.block >= pace.largest; }   // ... nor for rounds whose block the pace has shrunk
+    bool ext() const { return ext_ok && pace.block >= (flat ? flat : pace.largest); }   // ... nor for rounds whose block the pace has shrunk (below the largest FLAT block)
+    // Ring rounds (r6_ring). A stretch that may have them is paced with the ring block as its largest (the driver builds `pace` so) and
+    // carries the largest FLAT block here; 0: none in this stretch, block() is the pace's as ever. A round that is not a ring round —
+    // the stretch's tail, a shrunk block, rounds with a compact index — lies in LDS as a whole: at most `flat` tasks. (Ring rounds that
+    // decide less than 0.4 of their block make the pace shrink it; down to the flat block the rounds are what they are without a ring,
+    // long lists included, and the pace grows the block again when they fill it.)
+    uint32_t flat = 0;
+    bool ring_mounts = false;
+    uint32_t n_words = 0;
+    R6Knobs ring_knobs{};
+    bool ring() const { return flat != 0 && !cpt.on && pace.block >= pace.largest && r6_ring(ring_knobs, ext(), ring_mounts, true, n_words, pace.end - pace.pos, flat); }
+    uint32_t block() const { return (flat == 0 || ring()) ? pace.block : std::min<uint32_t>(pace.block, flat); }
     // The words behind a chunk. true: a stretch goes to the scan resolver, and the rounds behind it keep block and ext (no replan);
     // false: the next chunk and the next block are planned. `used` is taken before the pace moves on.
     bool after_rounds(const R6Words& w, uint32_t* used, double* recent) {
