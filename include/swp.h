@@ -294,7 +294,8 @@ typedef struct {
     uint32_t port_set;       /* 0 = HostPortFilter disabled */
     uint64_t max_replicas;   /* 0 = MaxReplicasFilter disabled (filter.go:363-370) */
     uint64_t spec_version;   /* SpecVersion.Index (0 when nil) — selects the failure bucket */
-    uint32_t spread_set;     /* 0 = no spread preferences (Placement.Preferences, nodeset.go:59-82) */
+    uint32_t spread_set;     /* 0 = no spread preferences (Placement.Preferences, nodeset.go:59-82). A group of swp_schedule_groups
+                                carries any set; a one-off task of a batch carries one within the limits stated at swp_schedule_batch */
     uint32_t generic_set;    /* 0 = no generic reservations (swp_generic_set); such a task needs SWP_TASK_RES_ENABLED */
 } swp_task_desc;             /* 64 bytes */
 
@@ -309,7 +310,19 @@ typedef struct {
  *   out_node[i]      node index or -1 ("no suitable node")
  *   out_fail_hist[i] per-filter first-failure counts over all nodes at the moment task i was
  *                    tried (what Pipeline.Explain reads, pipeline.go:84-103); only written for
- *                    tasks with out_node[i] == -1; may be NULL. */
+ *                    tasks with out_node[i] == -1; may be NULL.
+ * One-off tasks WITH spread preferences (spread_set != 0) are taken in their places: such a task is a group of one — nodeSet.tree with
+ * a heap of one per leaf, scheduleNTasksOnSubtree (scheduler.go:772-825) with n = 1 at the root — decided on the device between the
+ * tasks in front of it and behind it (a batch's spread segments, csrc/swp_scan_spread.hpp), its Explain row the plain first-fail
+ * histogram like any other task's. Limits, checked when the batch is prepared, on the nodeSet it is prepared for:
+ *   - at most 4 096 node slots;
+ *   - the node rows (24 bytes a slot) and the trees of the batch's spread sets — 32 bytes per branch of the largest tree, 20 per
+ *     branch of all of them, 32 per level — fit 160 KiB - 512 bytes of LDS (4 096 slots leave room for some 1 200 branches);
+ *   - no exception entry beyond the scan resolver's keys (256 recorded failures, 2^24 tasks of a service on a node).
+ * Outside them, for a task that has cluster mounts as well (SWP_TASK_MOUNTS), on a shard set and in the shard / rank protocols
+ * (swp_shard_*), the refusal is SWP_EUNSUPPORTED as before — the message names the limit — with engine and mirror untouched: such a task
+ * goes through swp_schedule_groups as a group of one. swp_fit_pairs* refuse templates with preferences as before.
+ * (swp_stats: a spread segment counts as a stretch of the scan resolver — scan_launches, scan_tasks, ms_scan.) */
 int swp_schedule_batch(swp_engine*, const swp_task_desc* tasks, uint32_t n_tasks,
                        int32_t* out_node, uint32_t* out_fail_hist /* [n_tasks][SWP_NFILTERS] */);
 
@@ -317,8 +330,8 @@ int swp_schedule_batch(swp_engine*, const swp_task_desc* tasks, uint32_t n_tasks
  * array order, scheduleTaskGroup with k = sizes[g] (scheduler.go:694-748): nodeSet.tree with a max-heap of k
  * per leaf (nodeset.go:50-124, container/heap order reproduced), scheduleNTasksOnSubtree (:772-825), the fill
  * loop scheduleNTasksOnNodes (:844-924) incl. the residual update. One descriptor per group (all tasks of a
- * group are identical for the filters, scheduler.go:696-702). Also the path of one-off tasks that carry spread
- * preferences (a group of one). (SURVEY.md 8b sketched this entry as swp_scan_groups — candidates out, tree walk and
+ * group are identical for the filters, scheduler.go:696-702). Also a path for one-off tasks that carry spread
+ * preferences (a group of one): the one for those a batch refuses (swp_schedule_batch: its limits). (SURVEY.md 8b sketched this entry as swp_scan_groups — candidates out, tree walk and
  * fill loop on the host; they run on the device as well, so the call returns placements.)
  *   out_node       Σ sizes entries, group after group, tasks in canonical (enqueue) order; -1 = left over
  *   out_fail_hist  [n_groups][SWP_NFILTERS]: Pipeline counters as noSuitableNode would read them
@@ -332,7 +345,9 @@ int swp_schedule_groups_volumes(swp_engine*, const swp_task_desc* groups, const 
                                 int32_t* out_node, uint32_t* out_fail_hist, uint32_t* out_att);
 
 /* The same in three steps so that a caller (bench.py) can time the device pass alone:
- *   prepare: de-duplicate predicate sets, upload descriptors and per-service state
+ *   prepare: de-duplicate predicate sets, upload descriptors and per-service state; accepts what swp_schedule_batch accepts — one-off
+ *            tasks with spread preferences within its limits included, the refusals are made here — and so does
+ *            swp_batch_prepare_templates. The trees of the spread sets are built from the nodeSet again when the batch runs.
  *   run:     kernels only (class bitmaps → scan → resolve/commit → explain); asynchronous
  *   fetch:   wait, copy results back, fold the placements into the host-side node mirror */
 typedef struct swp_batch swp_batch;
@@ -378,6 +393,8 @@ void swp_batch_free(swp_engine*, swp_batch*);
  *     prepare + run_streamed + fetch: the same holds for its first two steps; an error of the fetch step alone (a HIP error while the
  *     Explain rows or the attachments are copied back) is returned with the batch decided, delivered and in the mirror, as it is when
  *     swp_batch_fetch fails behind swp_batch_run_streamed.
+ *   - One-off tasks with spread preferences are taken as swp_schedule_batch takes them (its limits); a publish follows every spread
+ *     segment, as it follows every stretch of another resolver.
  *   - A shard set and the shard / rank protocols refuse these entries with SWP_EUNSUPPORTED (nothing is written); task groups
  *     are streamed by swp_schedule_groups_streamed below. */
 typedef int (*swp_prefix_sink)(void* ctx, uint32_t first, uint32_t count, const int32_t* nodes);
@@ -652,7 +669,8 @@ typedef struct {
     float    ms_propose, ms_apply;          /* Σ k_propose / k_shard_apply launch durations */
     uint32_t propose_launches, propose_tasks;   /* launches and Σ tasks proposed (a task cut off a block is proposed again) */
     uint32_t waterfill_tasks;   /* tasks placed as runs of identical tasks (k_waterfill), since swp_create */
-    uint32_t scan_tasks;        /* last batch: tasks the scan resolver decided (k_scan / k_scanb: stretches without plain candidates); scan_launches
+    uint32_t scan_tasks;        /* last batch: tasks the scan resolver decided (k_scan / k_scanb: stretches without plain candidates; k_scan_spread: the
+                                   spread segments of one-off tasks with spread preferences — the struct has no words left for counters of their own); scan_launches
                                    counts those stretches and ms_scan their time (SWP_CFG_PROFILE). A stretch that went through the compact
                                    instance — a cluster of more than 4 096 nodes, the union of the stretch's class rows at most that — is
                                    counted like any other, in both; a probe that refused a stretch is counted in neither */

@@ -34,6 +34,7 @@
 #include "swp_resolve7.hpp"
 #include "swp_rounds.hpp"
 #include "swp_scan.hpp"
+#include "swp_scan_spread.hpp"
 #include "swp_shard.hpp"
 #include "swp_waterfill.hpp"
 
@@ -398,6 +399,11 @@ inline uint64_t svcver_key(uint32_t svc, uint64_t ver) { return ((uint64_t)svc <
 
 }  // namespace
 
+struct SpreadTrees {   // the decision trees of a list of spread sets over the nodeSet (build_spread_trees)
+    std::vector<uint32_t> tree_off{0}, tn_parent, tn_first, tn_next, tn_nchild, tn_nodes, tn_depth, leaf_of;   // leaf_of: [trees][n_nodes], 0xFFFFFFFF: not in the nodeSet
+    uint32_t max_ntn = 1, max_depth = 0;
+};
+
 struct swp_batch {
     uint32_t T = 0;
     std::vector<swp_task_desc> tasks;      // the descriptors: one per task, or the caller's templates with task_tmpl naming each task's
@@ -461,8 +467,15 @@ struct swp_batch {
     DevBuf d_trows;                        // k_resolve6, task-rows mode: [block][n_words]
     DevBuf d_thr64, d_planes6, d_rr6, d_blk6;   // k_resolve6: raw thresholds, level planes, demand-class rows, control block
     // segments of the batch: runs of identical tasks (k_waterfill) and the stretches between them (the resolvers)
-    struct Seg { uint32_t j0, n; bool run; };
+    // ... and the spread segments (k_scan_spread, swp_rounds.hpp spread_segments): one-off tasks with spread preferences, one after the other
+    struct Seg { uint32_t j0, n; bool run; bool spread = false; };
     std::vector<Seg> segs;
+    // one-off tasks with spread preferences: sp_tree[task] = the task's tree among sp_sets' (tree 0 = spread set 0: no levels, one leaf);
+    // the trees themselves are built from the host mirror when the batch RUNS (labels may have moved since it was prepared)
+    bool has_spread = false;
+    std::vector<uint32_t> sp_sets, sp_tree;
+    SpreadTrees sp_trees;
+    DevBuf d_sp_tree, d_sp_off, d_sp_par, d_sp_first, d_sp_next, d_sp_nch, d_sp_depth, d_sp_leaf;
     bool wide_keys = false;                // an exception entry beyond the 8 + 24 bit keys of k_waterfill and the scan resolver: the block resolver decides alone
     DevBuf d_wf;                           // k_waterfill scratch: [3][n_nodes] u32
     // the streamed run (swp_batch_run_streamed, swp_publish.hpp): the host-visible block k_publish writes — the mark counter on a line
@@ -899,6 +912,67 @@ NodeView node_view(swp_engine* e) {
 template <class T>
 std::string bytes_of(const T* p, size_t n) { return std::string(reinterpret_cast<const char*>(p), n * sizeof(T)); }
 
+// The decision-tree topology of spread sets over the nodeSet as the host mirror holds it (nodeset.go:57-101): branch creation order =
+// node index order, the reference's canonical order. Per tree a range of tree nodes [tree_off[t], tree_off[t + 1]), local index 0 = the
+// root, a child behind its parent; a set without levels is a tree of one node. What the call for task groups (k_groups2) and a batch's
+// spread segments (k_scan_spread) both upload; tn_depth is the latter's alone.
+void build_spread_trees(const swp_engine* e, const std::vector<uint32_t>& tree_sets, SpreadTrees* out) {
+    const uint32_t N = e->n_nodes;
+    SpreadTrees& T = *out;
+    T = SpreadTrees{};
+    T.leaf_of.assign((size_t)tree_sets.size() * N, 0xFFFFFFFFu);
+    for (size_t t = 0; t < tree_sets.size(); ++t) {
+        const auto& levels = e->spread_sets[tree_sets[t]];
+        const uint32_t base = (uint32_t)T.tn_parent.size();
+        std::vector<uint32_t> last_child;   // per tnode: last child created (for sibling chaining)
+        auto new_node = [&](uint32_t parent, uint32_t depth) -> uint32_t {
+            uint32_t id = (uint32_t)T.tn_parent.size() - base;
+            T.tn_parent.push_back(parent);
+            T.tn_first.push_back(0xFFFFFFFFu);
+            T.tn_next.push_back(0xFFFFFFFFu);
+            T.tn_nchild.push_back(0);
+            T.tn_nodes.push_back(0);
+            T.tn_depth.push_back(depth);
+            last_child.push_back(0xFFFFFFFFu);
+            return id;
+        };
+        new_node(0xFFFFFFFFu, 0);
+        std::map<std::pair<uint32_t, uint32_t>, uint32_t> child_of;   // (tnode, raw value id) -> child
+        for (uint32_t n = 0; n < N; ++n) {
+            const HostNode& h = e->nodes[n];
+            if (!h.present) continue;
+            uint32_t tn = 0, depth = 0;
+            for (const swp_spread& lv : levels) {
+                uint32_t value = 0;
+                if (lv.kind == SWP_CK_NODE_LABEL) {
+                    if (h.row.flags & SWP_NODE_HAS_LABELS)
+                        for (const swp_kv& kv : h.labels)
+                            if (kv.key == lv.key) value = kv.raw;
+                } else if ((h.row.flags & SWP_NODE_HAS_DESC) && (h.row.flags & SWP_NODE_HAS_ENGINE) && (h.row.flags & SWP_NODE_HAS_ELABELS)) {
+                    for (const swp_kv& kv : h.elabels)
+                        if (kv.key == lv.key) value = kv.raw;
+                }
+                ++depth;
+                auto it = child_of.find({tn, value});
+                if (it == child_of.end()) {
+                    uint32_t c = new_node(tn, depth);
+                    if (last_child[tn] == 0xFFFFFFFFu) T.tn_first[base + tn] = c;
+                    else T.tn_next[base + last_child[tn]] = c;
+                    last_child[tn] = c;
+                    T.tn_nchild[base + tn]++;
+                    it = child_of.emplace(std::make_pair(tn, value), c).first;
+                }
+                tn = it->second;
+            }
+            T.leaf_of[t * N + n] = tn;
+            T.tn_nodes[base + tn]++;   // nodes of this leaf: its heap never holds more (nodeset.go:107-120)
+        }
+        T.tree_off.push_back((uint32_t)T.tn_parent.size());
+        T.max_ntn = std::max<uint32_t>(T.max_ntn, (uint32_t)T.tn_parent.size() - base);
+        T.max_depth = std::max<uint32_t>(T.max_depth, (uint32_t)levels.size());
+    }
+}
+
 // ---- batch construction -------------------------------------------------------------------------
 // tmpl_idx != nullptr: `descs` holds n_tmpl TEMPLATES and task i carries descs[tmpl_idx[i]] (swp_batch_prepare_templates): the caller has
 // done the de-duplication, the per-task pass is an array lookup instead of a hash of 64 bytes
@@ -1012,7 +1086,13 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
             return e->fail(SWP_EINVAL, "task %u references an unknown predicate set", i);
         if (d.service >= e->spaces[SWP_SPACE_SERVICE].strs.size()) return e->fail(SWP_EINVAL, "task %u: unknown service id %u", i, d.service);
         if (d.spread_set >= e->spread_sets.size()) return e->fail(SWP_EINVAL, "task %u references an unknown spread set", i);
-        if (d.spread_set && !weights) return e->fail(SWP_EUNSUPPORTED, "task %u has spread preferences: schedule it through swp_schedule_groups", i);
+        // a one-off task with spread preferences: a spread segment decides it (swp_scan_spread.hpp), within that kernel's limits
+        if (d.spread_set && !weights) {
+            if (e->n_nodes > scan_max_nodes())
+                return e->fail(SWP_EUNSUPPORTED, "task %u has spread preferences: schedule it through swp_schedule_groups (a batch takes them on at most %u node slots, this nodeSet has %u)", i, scan_max_nodes(), e->n_nodes);
+            if (d.flags >> SWP_TASK_MOUNTS_SHIFT)
+                return e->fail(SWP_EUNSUPPORTED, "task %u has spread preferences: schedule it through swp_schedule_groups (a batch takes none that also has cluster mounts)", i);
+        }
         if (d.generic_set >= e->gen_sets.size()) return e->fail(SWP_EINVAL, "task %u references an unknown generic set", i);
         if ((d.flags >> SWP_TASK_MOUNTS_SHIFT) >= e->mount_sets.size()) return e->fail(SWP_EINVAL, "task %u references an unknown mount set", i);
         // the exactness argument (feasibility only shrinks inside a batch) needs non-negative reservations; the API layer
@@ -1196,7 +1276,8 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
         uint32_t longest = 0, i = 0;
         while (i < T) {
             uint32_t k = i + 1;
-            const bool can = !(b->rt[i].flags & (RT_PORTS | RT_UNCOUNTED)) && !b->has_generic && !(tasks[i].flags >> SWP_TASK_MOUNTS_SHIFT);   // (a batch with generic reservations is decided by the block resolver alone; so is a task with cluster mounts)
+            const bool can = !(b->rt[i].flags & (RT_PORTS | RT_UNCOUNTED)) && !b->has_generic && !(tasks[i].flags >> SWP_TASK_MOUNTS_SHIFT) &&   // (a batch with generic reservations is decided by the block resolver alone; so is a task with cluster mounts)
+                             !(tasks[i].spread_set && !weights);   // (a one-off task with spread preferences: a spread segment)
             while (can && k < T && same(i, k)) ++k;
             const bool run = k - i >= run_min;
             if (run) {
@@ -1313,6 +1394,47 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
             b->segs = std::move(merged);
             if (!runs_left) b->segs.clear();
         }
+    }
+    // one-off tasks with spread preferences: each names a tree, and the stretches between the runs are cut into spread segments
+    // (swp_rounds.hpp spread_segments). The trees are built once here for the limit — the largest tree's words next to the node rows
+    // in the kernel's LDS — and again from the mirror when the batch runs.
+    b->has_spread = false;
+    b->sp_sets.clear();
+    b->sp_tree.clear();
+    if (!weights) {
+        for (uint32_t i = 0; i < T && !b->has_spread; ++i) b->has_spread = tasks[i].spread_set != 0;
+    }
+    if (b->has_spread) {
+        if (b->wide_keys)
+            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (a batch takes them with at most 255 recorded failures and fewer than 2^24 tasks of a service on a node)");
+        std::unordered_map<uint32_t, uint32_t> tree_local;
+        b->sp_sets.push_back(0);   // tree 0: no levels
+        tree_local.emplace(0u, 0u);
+        b->sp_tree.assign(T, 0);
+        for (uint32_t i = 0; i < T; ++i) {
+            const uint32_t ss = tasks[i].spread_set;
+            if (!ss) continue;
+            auto it = tree_local.find(ss);
+            if (it == tree_local.end()) {
+                it = tree_local.emplace(ss, (uint32_t)b->sp_sets.size()).first;
+                b->sp_sets.push_back(ss);
+            }
+            b->sp_tree[i] = it->second;
+        }
+        build_spread_trees(e, b->sp_sets, &b->sp_trees);
+        if (scan_spread_lds_size(e->n_nodes, b->sp_trees.max_ntn, b->sp_trees.max_depth, (uint32_t)b->sp_sets.size(), b->sp_trees.tree_off.back()) > R6_LDS_BUDGET)
+            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (%u node slots and trees of %u branches, the largest of %u over %u levels, exceed the spread kernel's LDS)",
+                           e->n_nodes, b->sp_trees.tree_off.back(), b->sp_trees.max_ntn, b->sp_trees.max_depth);
+        std::vector<swp_batch::Seg> cut;
+        auto kind = [&](uint32_t j) { return tasks[j].spread_set ? (int)SPREAD_TASK : (tasks[j].flags >> SWP_TASK_MOUNTS_SHIFT) ? (int)SPREAD_FENCE : (int)SPREAD_PLAIN; };
+        auto piece = [&](uint32_t j0, uint32_t n, bool spread) { cut.push_back(swp_batch::Seg{j0, n, false, spread}); };
+        if (b->segs.empty()) spread_segments(0u, T, kind, piece);
+        else
+            for (const swp_batch::Seg& sg : b->segs) {
+                if (sg.run) cut.push_back(sg);
+                else spread_segments(sg.j0, sg.j0 + sg.n, kind, piece);
+            }
+        b->segs = std::move(cut);
     }
 
     mark("exception lists + slots");
@@ -2055,6 +2177,83 @@ int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra
     return SWP_OK;
 }
 
+// A batch with spread segments, once per run and before its first launch: the trees of its spread sets from the nodeSet as the mirror
+// holds it NOW (the batch may have been prepared before a label moved), the limit checked again, the tables uploaded.
+int spread_tables(swp_engine* e, swp_batch* b) {
+    build_spread_trees(e, b->sp_sets, &b->sp_trees);
+    const SpreadTrees& t = b->sp_trees;
+    if (e->n_nodes > scan_max_nodes() || scan_spread_lds_size(e->n_nodes, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) > R6_LDS_BUDGET)
+        return e->fail(SWP_EUNSUPPORTED, "the batch has tasks with spread preferences: %u node slots and a tree of %u branches over %u levels exceed the spread kernel's LDS (swp_schedule_groups takes them)",
+                       e->n_nodes, t.max_ntn, t.max_depth);
+    int rc;
+    if ((rc = upload(e, b->d_sp_tree, b->sp_tree))) return rc;
+    if ((rc = upload(e, b->d_sp_off, t.tree_off))) return rc;
+    if ((rc = upload(e, b->d_sp_par, t.tn_parent))) return rc;
+    if ((rc = upload(e, b->d_sp_first, t.tn_first))) return rc;
+    if ((rc = upload(e, b->d_sp_next, t.tn_next))) return rc;
+    if ((rc = upload(e, b->d_sp_nch, t.tn_nchild))) return rc;
+    if ((rc = upload(e, b->d_sp_depth, t.tn_depth))) return rc;
+    return upload(e, b->d_sp_leaf, t.leaf_of);
+}
+
+// A spread segment [j0, j1): one-off tasks with spread preferences (and the few plain tasks between them), one after the other, by
+// k_scan_spread over the (service, node) matrices k_scan_fill / k_scan_lists build from the lists as they are. The node rows, the lists
+// and the logs come out as the scan resolver leaves them; the block resolver's bitmaps are NOT rebuilt here — a stretch of rounds
+// behind the segment builds them from the node rows when it begins (stretch_begin), a k_waterfill run reads none — so a batch that is
+// all spread segments never meets the block resolver's limit on the nodes' task-count spread. Streamed: a publish behind the segment.
+int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_t j1) {
+    hipStream_t st = e->stream;
+    R6Args ra{};
+    if (int rc = r6_args_for(e, b, run.largest(), run.task_rows, run.knobs, &ra)) return rc;
+    SpreadArgs sp{};
+    ScanArgs& sa = sp.s;
+    sa.a = ra;
+    sa.j0 = j0;
+    sa.j1 = j1;
+    sa.n_svc = b->n_svc;
+    sa.n_sc = b->n_sc;
+    HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * e->n_nodes * 4));
+    HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * e->n_nodes * 4));
+    sa.hmat = b->d_hmat.as<uint32_t>();
+    sa.emat = b->d_emat.as<uint32_t>();
+    sp.ttree = b->d_sp_tree.as<uint32_t>();
+    sp.tree_off = b->d_sp_off.as<uint32_t>();
+    sp.tn_parent = b->d_sp_par.as<uint32_t>();
+    sp.tn_first = b->d_sp_first.as<uint32_t>();
+    sp.tn_next = b->d_sp_next.as<uint32_t>();
+    sp.tn_nchild = b->d_sp_nch.as<uint32_t>();
+    sp.tn_depth = b->d_sp_depth.as<uint32_t>();
+    sp.leaf_of_node = b->d_sp_leaf.as<uint32_t>();
+    sp.max_ntn = b->sp_trees.max_ntn;
+    sp.max_depth = b->sp_trees.max_depth;
+    sp.n_trees = (uint32_t)b->sp_sets.size();
+    sp.tot_ntn = b->sp_trees.tree_off.back();
+    HIPCHECK(e, hipMemsetAsync(b->d_blk6.p, 0, sizeof(Blk6), st));   // (no error; the kernel leaves the position at j1)
+    if (run.prof) {
+        if (int rc = grow_events(e, e->ev_scan, (size_t)e->ev_scan_used + 2)) return rc;
+        HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used], st));
+    }
+    hipError_t r = launch_scan_matrices(sa, st);
+    if (r == hipSuccess) r = launch_scan_spread(sp, st, e->device);
+    if (run.prof) {
+        HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used + 1], st));
+        e->ev_scan_used += 2;
+    }
+    if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan_spread launch: %s", hipGetErrorString(r));
+    e->scan_tasks_batch += j1 - j0;   // (swp_stats_t has no words left: a spread segment counts as a scan stretch)
+    e->scan_stretches_batch += 1;
+    if (run.sx)
+        if (int rc = stream_publish(e, run.sx, &b->d_blk6.as<Blk6>()->pos, 0)) return rc;
+    Blk6 hb{};
+    if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
+    if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
+    if (hb.error == ERR_LEVEL_RANGE) return e->fail(SWP_ERANGE, "a node holds 2^20 tasks or more: beyond the scan resolver's packed key");
+    if (hb.error != ERR_NONE) return e->fail(SWP_EHIP, "k_scan_spread: the walk of a task did not end within its bound (error %u)", hb.error);
+    if (hb.pos != j1) return e->fail(SWP_EHIP, "k_scan_spread stopped at task %u of [%u, %u)", hb.pos, j0, j1);
+    if (run.knobs.dbg & 16) fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u): trees of at most %u branches over %u levels\n", j0, j1, sp.max_ntn, sp.max_depth);
+    return SWP_OK;
+}
+
 // SWP_DBG=16: the commit kernel's section timers of a control block, per round. sharded: k_r7_commit's, which folds in its prologue and
 // has no wave waiting for the matcher.
 void r6_report(const Blk6& hb, bool sharded) {
@@ -2272,10 +2471,15 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     if (rc) return rc;
     if (run.prof) HIPCHECK(e, hipEventRecord(e->ev[1], st));
     if ((rc = r6_run_plan(e, b, &run))) return rc;
+    if (b->has_spread && (rc = spread_tables(e, b))) return rc;
     if (b->segs.empty()) rc = run_stretch(e, b, run, 0, T);
     else {
         HIPCHECK(e, b->d_wf.reserve((size_t)3 * N * 4));
         for (const swp_batch::Seg& sg : b->segs) {
+            if (sg.spread) {
+                if ((rc = spread_segment(e, b, run, sg.j0, sg.j0 + sg.n))) break;
+                continue;
+            }
             if (!sg.run) {
                 if ((rc = run_stretch(e, b, run, sg.j0, sg.j0 + sg.n))) break;
                 continue;
@@ -3369,56 +3573,11 @@ static int schedule_groups_impl(swp_engine* e, const swp_task_desc* groups, cons
             tree_local[groups[g].spread_set] = (uint32_t)tree_sets.size();
             tree_sets.push_back(groups[g].spread_set);
         }
-    std::vector<uint32_t> tree_off{0}, tn_parent, tn_first, tn_next, tn_nchild, tn_nodes, leaf_of((size_t)tree_sets.size() * N, 0xFFFFFFFFu);
-    uint32_t max_ntn = 1, max_depth = 0;
-    for (size_t t = 0; t < tree_sets.size(); ++t) {
-        const auto& levels = e->spread_sets[tree_sets[t]];
-        const uint32_t base = (uint32_t)tn_parent.size();
-        std::vector<uint32_t> last_child;   // per tnode: last child created (for sibling chaining)
-        auto new_node = [&](uint32_t parent) -> uint32_t {
-            uint32_t id = (uint32_t)tn_parent.size() - base;
-            tn_parent.push_back(parent);
-            tn_first.push_back(0xFFFFFFFFu);
-            tn_next.push_back(0xFFFFFFFFu);
-            tn_nchild.push_back(0);
-            tn_nodes.push_back(0);
-            last_child.push_back(0xFFFFFFFFu);
-            return id;
-        };
-        new_node(0xFFFFFFFFu);
-        std::map<std::pair<uint32_t, uint32_t>, uint32_t> child_of;   // (tnode, raw value id) -> child
-        for (uint32_t n = 0; n < N; ++n) {
-            const HostNode& h = e->nodes[n];
-            if (!h.present) continue;
-            uint32_t tn = 0;
-            for (const swp_spread& lv : levels) {
-                uint32_t value = 0;
-                if (lv.kind == SWP_CK_NODE_LABEL) {
-                    if (h.row.flags & SWP_NODE_HAS_LABELS)
-                        for (const swp_kv& kv : h.labels)
-                            if (kv.key == lv.key) value = kv.raw;
-                } else if ((h.row.flags & SWP_NODE_HAS_DESC) && (h.row.flags & SWP_NODE_HAS_ENGINE) && (h.row.flags & SWP_NODE_HAS_ELABELS)) {
-                    for (const swp_kv& kv : h.elabels)
-                        if (kv.key == lv.key) value = kv.raw;
-                }
-                auto it = child_of.find({tn, value});
-                if (it == child_of.end()) {
-                    uint32_t c = new_node(tn);
-                    if (last_child[tn] == 0xFFFFFFFFu) tn_first[base + tn] = c;
-                    else tn_next[base + last_child[tn]] = c;
-                    last_child[tn] = c;
-                    tn_nchild[base + tn]++;
-                    it = child_of.emplace(std::make_pair(tn, value), c).first;
-                }
-                tn = it->second;
-            }
-            leaf_of[t * N + n] = tn;
-            tn_nodes[base + tn]++;   // nodes of this leaf: its heap never holds more (nodeset.go:107-120)
-        }
-        tree_off.push_back((uint32_t)tn_parent.size());
-        max_ntn = std::max<uint32_t>(max_ntn, (uint32_t)tn_parent.size() - base);
-        max_depth = std::max<uint32_t>(max_depth, (uint32_t)levels.size());
-    }
+    SpreadTrees trees;
+    build_spread_trees(e, tree_sets, &trees);
+    const std::vector<uint32_t>&tree_off = trees.tree_off, &tn_parent = trees.tn_parent, &tn_first = trees.tn_first, &tn_next = trees.tn_next, &tn_nchild = trees.tn_nchild,
+                               &tn_nodes = trees.tn_nodes, &leaf_of = trees.leaf_of;
+    const uint32_t max_ntn = trees.max_ntn, max_depth = trees.max_depth;
     std::vector<GroupRec2> recs(n_groups);
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> scls_ids;   // static classes: the distinct (plugin, constraint, platform) class triples
     std::vector<uint32_t> scls_def;
@@ -3872,6 +4031,7 @@ int swp_shard_begin(swp_engine* e, swp_batch* b) {
         return e->fail(SWP_EINVAL, "the nodeSet grew from %u to %u node slots since swp_batch_prepare: prepare the batch again", b->n_nodes_prepared, e->n_nodes);
     if (b->has_generic) return e->fail(SWP_EUNSUPPORTED, "generic reservations are not part of the HOST-merged shard protocol (swp_shard_run / swp_shard_run_rank carry them)");
     if (!b->csi_set.empty()) return e->fail(SWP_EUNSUPPORTED, "tasks with cluster mounts are not part of the HOST-merged shard protocol (swp_shard_run / swp_shard_run_rank carry them)");
+    if (b->has_spread) return e->fail(SWP_EUNSUPPORTED, "tasks with spread preferences are not part of the shard protocols: a shard sees a part of the nodeSet (swp_schedule_groups on one engine or a shard set)");
     b->shard_open = true;
     b->shard_ncommit = b->shard_ninf = 0;
     e->stats.ms_propose = e->stats.ms_apply = 0.f;
@@ -4223,6 +4383,7 @@ int swp_shard_run(swp_engine* const* engines, swp_batch* const* batches, uint32_
     for (uint32_t g = 0; g < G; ++g) {
         if (!engines[g] || !batches[g] || batches[g]->T != T) return e0->fail(SWP_EINVAL, "shard %u: every shard's batch must hold the same %u tasks", g, T);
         if (engines[g]->n_nodes != batches[g]->n_nodes_prepared) return e0->fail(SWP_EINVAL, "shard %u: the nodeSet grew since swp_batch_prepare", g);
+        if (batches[g]->has_spread) return e0->fail(SWP_EUNSUPPORTED, "tasks with spread preferences are not part of the shard protocols: a shard sees a part of the nodeSet (swp_schedule_groups)");
         for (uint32_t h = 0; h < g; ++h)
             if (engines[h] == engines[g]) return e0->fail(SWP_EINVAL, "shards %u and %u name the same engine", h, g);
     }
@@ -4564,6 +4725,7 @@ int swp_shard_run_rank(swp_engine* e, swp_batch* b, const uint32_t* shard_nodes,
     Blk6 hb{};
     int pre = SWP_OK;
     if (e->n_nodes != b->n_nodes_prepared) pre = e->fail(SWP_EINVAL, "the nodeSet grew since swp_batch_prepare");
+    else if (b->has_spread) pre = e->fail(SWP_EUNSUPPORTED, "tasks with spread preferences are not part of the shard protocols: a shard sees a part of the nodeSet (swp_schedule_groups)");
     else if (shard_nodes[me] != e->n_nodes) pre = e->fail(SWP_EINVAL, "rank %u holds %u node slots, shard_nodes says %u", me, e->n_nodes, shard_nodes[me]);
     else if (e->n_nodes == 0) pre = e->fail(SWP_EINVAL, "rank %u owns no node", me);
     else if (r6_propose_lds_size(Wn) > R6_LDS_BUDGET) pre = e->fail(SWP_ERANGE, "%u nodes exceed the block resolver's LDS", e->n_nodes);

@@ -62,6 +62,11 @@ hipError_t launch_scan(const ScanArgs& s, hipStream_t st, int dev, bool node_loc
 hipError_t launch_scan_probe(const ScanArgs& s, hipStream_t st);                // the compact instance: the union of the stretch's class rows, *s.cnc its node count
 bool scan_batched_fits_c(uint32_t n_c, uint32_t n_svc, uint32_t n_sc);          // ... k_scanb's compact form takes a node-local stretch over a union of n_c nodes: its rows fit in LDS and the union is small enough (or SWP_SCANB_COMPACT=1)
 hipError_t launch_scan_compact(const ScanArgs& s, hipStream_t st, int dev, bool node_local);   // ... and the stretch over it (s.n_c as read from the probe, <= scan_max_nodes()); node_local: as for launch_scan
+hipError_t launch_scan_matrices(const ScanArgs& s, hipStream_t st);             // k_scan_fill + k_scan_lists alone: the (service, node) matrices over all nodes
+// its spread instance: one-off tasks with spread preferences (swp_scan_spread.hpp, built in swp_scan_spread.hip)
+struct SpreadArgs;
+size_t scan_spread_lds_size(uint32_t n_nodes, uint32_t max_ntn, uint32_t max_depth, uint32_t n_trees, uint32_t tot_ntn);   // the kernel's LDS for these node slots, the largest / deepest tree and all trees' tables
+hipError_t launch_scan_spread(const SpreadArgs& p, hipStream_t st, int dev);    // behind launch_scan_matrices
 
 // task groups (swp_groups.hip)
 struct Groups2Args;

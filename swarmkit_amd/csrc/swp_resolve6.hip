@@ -197,6 +197,13 @@ hipError_t launch_scan(const ScanArgs& s, hipStream_t st, int dev, bool node_loc
     return launch_scan_nq<false>(s, scan_lds(s.a.n_nodes), st, dev);
 }
 
+// the matrices alone (what the spread instance, swp_scan_spread.hip, runs on)
+hipError_t launch_scan_matrices(const ScanArgs& s, hipStream_t st) {
+    hipLaunchKernelGGL(k_scan_fill, dim3(1024), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(k_scan_lists, dim3(64, s.n_svc), dim3(256), 0, st, s);
+    return hipGetLastError();
+}
+
 // ---- the compact instance: a cluster beyond SCAN_MAXN nodes, a stretch whose class rows' union is not ----
 // the probe: which class rows the tasks [j0, j1) name, their union, its node count (*s.cnc: the caller reads it), prefix sums and map
 hipError_t launch_scan_probe(const ScanArgs& s, hipStream_t st) {

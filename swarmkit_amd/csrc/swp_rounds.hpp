@@ -377,4 +377,37 @@ inline uint32_t group_marks(const uint32_t* sizes, uint32_t n_groups, uint32_t s
     return marks;
 }
 
+// One-off tasks with spread preferences inside a batch (swp_scan_spread.hpp): the SPREAD SEGMENTS of a range of tasks [j0, j1).
+// kind(j): SPREAD_PLAIN — the task has no preferences and the spread kernel could take it as a tree of one leaf; SPREAD_TASK — it has
+// preferences; SPREAD_FENCE — the spread kernel cannot take it (cluster mounts): it is never inside a segment.
+// A segment STARTS at a task with preferences and ENDS in front of the first fence, or in front of the first run of at least
+// SPREAD_GAP consecutive plain tasks, or at j1 — fewer plain tasks than that between two tasks with preferences, or behind the last
+// one, ride along. Exactness does not depend on the rule (a plain task gets the same node from either resolver); hand-over cost does:
+// a stretch of the block resolver behind a segment costs a rebuild of its bitmaps, its first rounds and a look at the control block
+// — some 50 - 100 us, what the spread kernel needs for a few dozen tasks at its ~2 us each.
+// on_seg(first, count, spread) for every piece of [j0, j1), in order, the pieces between segments included; returns the spread segments.
+enum { SPREAD_PLAIN = 0, SPREAD_TASK = 1, SPREAD_FENCE = 2 };
+constexpr uint32_t SPREAD_GAP = 64;
+template <class K, class F>
+inline uint32_t spread_segments(uint32_t j0, uint32_t j1, K kind, F on_seg) {
+    uint32_t n_seg = 0, plain0 = j0;   // plain0: where the piece in front of the next segment starts
+    for (uint32_t j = j0; j < j1;) {
+        if (kind(j) != SPREAD_TASK) { ++j; continue; }
+        uint32_t end = j + 1, gap = 0;   // end: one past the last task that is certainly inside; gap: plain tasks seen behind it
+        for (uint32_t k = j + 1; k < j1; ++k) {
+            const int c = kind(k);
+            if (c == SPREAD_FENCE) break;
+            if (c == SPREAD_TASK) { end = k + 1; gap = 0; continue; }
+            if (++gap >= SPREAD_GAP) break;
+            if (k + 1 == j1) end = j1;   // (a short tail rides along)
+        }
+        if (j > plain0) on_seg(plain0, j - plain0, false);
+        on_seg(j, end - j, true);
+        ++n_seg;
+        plain0 = j = end;
+    }
+    if (j1 > plain0) on_seg(plain0, j1 - plain0, false);
+    return n_seg;
+}
+
 }  // namespace swpdev

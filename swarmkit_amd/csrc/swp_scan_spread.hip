@@ -1,0 +1,33 @@
+// swp_scan_spread.hip — translation unit of k_scan_spread (swp_scan_spread.hpp) and its launcher. A unit of its own: the scan
+// resolver's shipped instances (swp_resolve6.hip) are compiled without it.
+#include <hip/hip_runtime.h>
+
+#include "swp_launch.hpp"
+#include "swp_wave.hpp"
+#include "swp_resolve6.hpp"
+#define SWP_SCAN_SPREAD_KERNEL
+#include "swp_scan_spread.hpp"
+
+namespace swpdev {
+
+size_t scan_spread_lds_size(uint32_t n_nodes, uint32_t max_ntn, uint32_t max_depth, uint32_t n_trees, uint32_t tot_ntn) { return scan_lds_sp(n_nodes, max_ntn, max_depth, n_trees, tot_ntn); }
+
+template <int NQ>
+static hipError_t launch_scan_spread_as(const SpreadArgs& p, size_t lds, hipStream_t st, int dev) {
+    hipError_t r;
+    if (lds > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(&k_scan_spread<NQ>), dev)) != hipSuccess) return r;
+    hipLaunchKernelGGL((k_scan_spread<NQ>), dim3(1), dim3(SCAN_THREADS), lds, st, p);
+    return hipGetLastError();
+}
+// the tasks [p.s.j0, p.s.j1) one after the other; p.s.hmat / emat as launch_scan_matrices left them
+hipError_t launch_scan_spread(const SpreadArgs& p, hipStream_t st, int dev) {
+    const size_t lds = scan_lds_sp(p.s.a.n_nodes, p.max_ntn, p.max_depth, p.n_trees, p.tot_ntn);
+    if (p.s.a.n_nodes == 0 || p.s.a.n_nodes > SCAN_MAXN || lds > (size_t)160 * 1024 - 512) return hipErrorInvalidValue;
+    switch (scan_nq(p.s.a.n_nodes)) {
+        case 1: return launch_scan_spread_as<1>(p, lds, st, dev);
+        case 2: return launch_scan_spread_as<2>(p, lds, st, dev);
+        default: return launch_scan_spread_as<4>(p, lds, st, dev);
+    }
+}
+
+}  // namespace swpdev

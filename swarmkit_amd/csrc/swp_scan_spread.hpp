@@ -1,0 +1,323 @@
+// swp_scan_spread.hpp — the SPREAD instance of the scan resolver: one-off tasks whose Placement.Preferences create spread levels, decided
+// inside a batch, one after the other, by ALL threads of one workgroup over ALL nodes (k_scan with one more reduction dimension).
+//
+// What the reference does for such a task (a group of ONE: scheduler.go:696-748): nodeSet.tree with maxAssignments = 1 (nodeset.go:50-124)
+// — every node of the nodeSet adds its ActiveTasksCountByService to every branch on its path, whether it passes the filters or not
+// (:88-90, :103-105), and every leaf's heap of one ends up with the leaf's least node by nodeLess among those that pass, the FIRST one
+// in node order among equals (:115 is strict; the canonical node order is the index order) — and then scheduleNTasksOnSubtree
+// (scheduler.go:772-825) with n = 1 at the root. With one task in the group the first leaf that holds a node takes it
+// (scheduleNTasksOnNodes places it on nodes[0] and the group map is empty: whatever the walk does afterwards changes nothing), so the walk
+// is run literally up to that leaf: desired / remainder / noRoom / tasksInUsableBranches per frame, the children in creation order
+// (tn_first / tn_next: first seen in node order), a child called with the tasksToAssign its parent computed (which may be more than one:
+// the branch that is handed five tasks spreads five over ITS children). A task without preferences is a tree of one node, the same path.
+//
+// Per task: every thread evaluates its nodes by k_scan's filter lines and k_scan's packed key (hi << 32 | total << 12 | node) and puts a
+// feasible node's key into leafmin[leaf of the node] (LDS min) and every present node's count of the service into tsum[leaf] (LDS add);
+// barrier; wave 0 adds the sums up the tree (a level at a time, deepest first) and its first lane walks; barrier; the owner of the
+// picked node applies NodeInfo.addTask exactly as k_scan does. The per-tree words (leafmin, tsum, noroom) exist twice and alternate
+// between tasks: the set of the NEXT task is cleared in front of this task's first barrier (its last reader, the walk two tasks ago,
+// ended in front of that task's second barrier). An unplaced task goes to inf_task / inf_pos: nothing passed in any leaf, so tree()
+// called the pipeline on every node of the nodeSet once — the batch's Explain pass is the plain first-fail histogram, unchanged.
+//
+// Written against swp_wave.hpp only (tests/emu/emu_scan_spread.cpp runs it on CPU fibers against a sequential model).
+#pragma once
+#include "swp_scan.hpp"
+
+namespace swpdev {
+
+#define ERR_SPREAD_WALK 4   // the walk of a task exceeded its bound of passes (it converges: a bug, or tables that are no tree): the launch goes on, the batch fails
+
+struct SpreadArgs {
+    ScanArgs s;             // the stretch [j0, j1), the (service, node) matrices of k_scan_fill / k_scan_lists over all nodes
+    const u32* ttree;       // [tasks of the batch] the task's tree (a task without preferences: the tree of no levels)
+    const u32* tree_off;    // [trees + 1] first tree node of a tree; the tables below are indexed by tree_off[tree] + local index, local 0 = the root
+    const u32* tn_parent;   // local index of the parent (the root: 0xFFFFFFFF); a child follows its parent in the table
+    const u32* tn_first;    // first child in creation order, 0xFFFFFFFF: a leaf
+    const u32* tn_next;     // next sibling in creation order
+    const u32* tn_nchild;   // len(tree.next)
+    const u32* tn_depth;    // levels above the tree node (the root: 0)
+    const u32* leaf_of_node;   // [trees][n_nodes] local index of the node's leaf, 0xFFFFFFFF: the node is not in the nodeSet
+    u32 max_ntn, max_depth; // over the batch's trees: tree nodes of the largest, levels of the deepest
+    u32 n_trees, tot_ntn;   // trees; tree nodes of all of them (tree_off[n_trees]): the tables' length — the kernel keeps them in LDS
+};
+
+struct SpFrame {   // one invocation of scheduleNTasksOnSubtree that went past the leaf test (scheduler.go:784-822)
+    i64 usable, desired, rem;   // tasksInUsableBranches, desiredTasksPerBranch, remainder
+    u32 tn, child, n_noroom, converging;
+};
+// node rows + the result word + two sets of (leafmin, tsum, noroom) per tree node of the largest tree + a frame per level + the trees'
+// tables (tree_off and the five per-tree-node words: the walk is a chain of dependent reads, a global round trip each otherwise)
+inline __host__ __device__ size_t scan_lds_sp(u32 n_nodes, u32 max_ntn, u32 max_depth, u32 n_trees, u32 tot_ntn) {
+    return (((size_t)n_nodes * 24 + 15) & ~(size_t)15) + 16 + (size_t)2 * max_ntn * 16 + (size_t)(max_depth + 1) * sizeof(SpFrame) + ((size_t)n_trees + 1 + (size_t)5 * tot_ntn) * 4;
+}
+
+#ifdef SWP_SCAN_SPREAD_KERNEL
+// scheduleNTasksOnSubtree with one task, up to the first leaf that holds a node: its key (KEY_NONE: no leaf does). One thread.
+// tn_first / tn_next / tn_nchild: the tree's own rows of the tables (local indices); max_depth: the frames there are
+WV_DEV u64 spread_walk(const u32* tn_first, const u32* tn_next, const u32* tn_nchild, u32 max_depth, u32 ntn, const u64* leafmin, const u32* tsum, u32* noroom, SpFrame* st, bool* hang) {
+    if (tn_first[0] == LIST_EMPTY) return leafmin[0];   // the tree is one leaf
+    int sp = 0;
+    u32 passes = 0;
+    st[0].tn = 0;
+    st[0].usable = tsum[0];
+    st[0].n_noroom = 0;
+    st[0].converging = 1;
+    st[0].child = LIST_EMPTY;
+    // tasksScheduled is 0 in every frame until a leaf takes the task, and then the walk is over: `remainder` never drops, and a frame's n
+    // — the tasksToAssign of the call that made it — can be computed again from the caller's frame whenever the frame needs it
+    bool fresh = true;   // the frame on top starts a pass of its while loop
+    while (sp >= 0) {
+        SpFrame& f = st[sp];
+        const u32 nch = tn_nchild[f.tn];
+        if (fresh) {   // `for tasksScheduled != n && len(noRoom) != len(tree.next) && converging`
+            i64 n = 1;
+            if (sp > 0) {
+                const SpFrame& up = st[sp - 1];
+                n = up.desired - (i64)tsum[f.tn] + (up.rem > 0 ? 1 : 0);
+            }
+            const i64 room = (i64)nch - (i64)f.n_noroom;
+            if (room == 0 || !f.converging) {   // returns 0: the caller notes noRoom
+                --sp;
+                if (sp >= 0) {
+                    SpFrame& up = st[sp];
+                    noroom[up.child] = 1;
+                    up.n_noroom++;
+                    up.usable -= (i64)tsum[up.child];
+                    up.child = tn_next[up.child];
+                    fresh = false;
+                }
+                continue;
+            }
+            if (++passes > 2u * ntn) { *hang = true; return KEY_NONE; }
+            const i64 tot = f.usable + n;
+            f.desired = tot / room;
+            f.rem = tot % room;
+            f.converging = 0;
+            f.child = tn_first[f.tn];
+            fresh = false;
+        }
+        // `for _, subtree := range tree.next` in creation order, from f.child on
+        bool called = false;
+        while (f.child != LIST_EMPTY) {
+            const u32 c = f.child;
+            if (!noroom[c]) {
+                const i64 sub = tsum[c];
+                if (sub < f.desired || (sub == f.desired && f.rem > 0)) {
+                    f.converging = 1;
+                    if (tn_first[c] == LIST_EMPTY) {   // a leaf: it takes the task iff its heap holds a node
+                        if (leafmin[c] != KEY_NONE) return leafmin[c];
+                        noroom[c] = 1;   // res = 0 < tasksToAssign
+                        f.n_noroom++;
+                        f.usable -= sub;
+                    } else {
+                        if ((u32)sp + 1u > max_depth) { *hang = true; return KEY_NONE; }   // (a frame per level: deeper than the tables say)
+                        SpFrame& d = st[sp + 1];
+                        d.tn = c;
+                        d.usable = sub;
+                        d.n_noroom = 0;
+                        d.converging = 1;
+                        d.child = LIST_EMPTY;
+                        ++sp;
+                        fresh = true;
+                        called = true;
+                        break;
+                    }
+                }
+            }
+            f.child = tn_next[c];
+        }
+        if (!called) fresh = true;   // the range is through: the while condition again
+    }
+    return KEY_NONE;
+}
+
+template <int SCAN_NQ>
+WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
+    const ScanArgs& s = p.s;
+    const R6Args& a = s.a;
+    const u32 tid = wv::tid(), lane = wv::lane(), N = a.n_nodes, Wn = a.n_words, M = p.max_ntn;
+    unsigned char* l = reinterpret_cast<unsigned char*>(wv::lds());
+    i64* cpu = reinterpret_cast<i64*>(l);
+    i64* mem = cpu + N;
+    u32* tot = reinterpret_cast<u32*>(mem + N);
+    int32_t* lastc = reinterpret_cast<int32_t*>(tot + N);
+    u64* res = reinterpret_cast<u64*>(l + (((size_t)N * 24 + 15) & ~(size_t)15));   // [2] the walk's answer, alternating
+    u64* lmin = res + 2;                                   // [2][M] a leaf's least key
+    u32* lsum = reinterpret_cast<u32*>(lmin + 2 * (size_t)M);   // [2][M] tree.tasks
+    u32* lnor = lsum + 2 * (size_t)M;                      // [2][M] noRoom
+    SpFrame* frames = reinterpret_cast<SpFrame*>(lnor + 2 * (size_t)M);   // [max_depth + 1]
+    u32* l_off = reinterpret_cast<u32*>(frames + p.max_depth + 1);       // [n_trees + 1] tree_off
+    u32* l_parent = l_off + p.n_trees + 1;                                // [tot_ntn] each: the trees' tables
+    u32* l_first = l_parent + p.tot_ntn;
+    u32* l_next = l_first + p.tot_ntn;
+    u32* l_nchild = l_next + p.tot_ntn;
+    u32* l_depth = l_nchild + p.tot_ntn;
+    if (a.blk->error != ERR_NONE) return;
+    for (u32 n = tid; n < N; n += SCAN_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
+    for (u32 i = tid; i < 2 * M; i += SCAN_THREADS) { lmin[i] = KEY_NONE; lsum[i] = 0; lnor[i] = 0; }
+    for (u32 i = tid; i <= p.n_trees; i += SCAN_THREADS) l_off[i] = p.tree_off[i];
+    for (u32 i = tid; i < p.tot_ntn; i += SCAN_THREADS) {
+        l_parent[i] = p.tn_parent[i]; l_first[i] = p.tn_first[i]; l_next[i] = p.tn_next[i]; l_nchild[i] = p.tn_nchild[i]; l_depth[i] = p.tn_depth[i];
+    }
+    u32 present = 0;   // bit q: this thread's q-th node is in the nodeSet
+    WV_UNROLL
+    for (int q = 0; q < SCAN_NQ; ++q) {
+        const u32 n = tid + (u32)q * SCAN_THREADS;
+        if (n < N && ((a.valid[n >> 6] >> (n & 63)) & 1ull)) present |= 1u << q;
+    }
+    u32 nc = a.ctl->ncommit, ni = a.ctl->ninf;
+    // What a task reads from global memory is requested AHEAD, as k_scan does: the three words that say where the rest lies — its
+    // class row, its service, its tree — two tasks ahead (the record's cache line comes with them); what hangs on those three — the static-class word, the key
+    // half, the list entry and the leaf of each of this thread's nodes — one task ahead. A task's turn then starts with everything in
+    // registers. The one value the task in between can change, the key half (and the entry) of the node it takes, is corrected by
+    // that node's owner.
+    const u32 first = s.j0 < s.j1 ? s.j0 : 0u, last = s.j0 < s.j1 ? s.j1 - 1u : 0u;   // (reads beyond the stretch are clamped to its last task and never used)
+    const u32 second = s.j0 + 1u < s.j1 ? s.j0 + 1u : last;
+    u32 sc_n = a.rt[first].sc, svc_n = a.rt[first].svc, tree_n = p.ttree[first];
+    u32 sc_nn = a.rt[second].sc, svc_nn = a.rt[second].svc, tree_nn = p.ttree[second];
+    u64 scn[SCAN_NQ];
+    u32 hin[SCAN_NQ], ein[SCAN_NQ], lfn[SCAN_NQ];
+    auto ahead = [&](u32 sc_, u32 svc_, u32 tree_) {   // this thread's nodes for the task with this class row, service and tree
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS;
+            const bool in = (present >> q) & 1u;
+            scn[q] = in ? a.sc[(size_t)sc_ * Wn + (n >> 6)] : 0ull;
+            hin[q] = in ? s.hmat[(size_t)svc_ * N + n] : 0u;
+            ein[q] = in ? s.emat[(size_t)svc_ * N + n] : LIST_EMPTY;
+            lfn[q] = in ? p.leaf_of_node[(size_t)tree_ * N + n] : LIST_EMPTY;
+        }
+    };
+    ahead(sc_n, svc_n, tree_n);
+    wv::barrier();
+    for (u32 t = s.j0; t < s.j1; ++t) {
+        const RTask r = a.rt[t];   // (its cache line was touched two tasks ago, for the three words)
+        const u32 set = (t - s.j0) & 1u, tree = tree_n, tbase = l_off[tree], ntn = l_off[tree + 1] - tbase;
+        u32 hiq[SCAN_NQ], enq[SCAN_NQ];   // (the owner of the pick needs its key half and list entry again)
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) { hiq[q] = hin[q]; enq[q] = ein[q]; }
+        u64* leafmin = lmin + (size_t)set * M;
+        u32* tsum = lsum + (size_t)set * M;
+        u32* noroom = lnor + (size_t)set * M;
+        const u32 gset = a.n_rg ? a.tg[t] : 0u;
+        // the next task's set (last read by the walk two tasks ago, in front of that task's second barrier)
+        for (u32 i = tid; i < M; i += SCAN_THREADS) { lmin[(size_t)(set ^ 1u) * M + i] = KEY_NONE; lsum[(size_t)(set ^ 1u) * M + i] = 0; lnor[(size_t)(set ^ 1u) * M + i] = 0; }
+        // ---- every thread: its nodes into their leaves
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS;
+            if (!((present >> q) & 1u)) continue;
+            const u32 w = n >> 6;
+            const u64 bit = 1ull << (n & 63);
+            const u32 hi = hiq[q], lf = lfn[q];
+            if (lf >= ntn) continue;   // (tables of another nodeSet: the launcher builds them from the one the batch was prepared for)
+            if (hi & 0xFFFFFFu) wv::lds_add32(tsum + lf, hi & 0xFFFFFFu);   // tree.tasks: every node of the nodeSet, feasible or not
+            if (!(scn[q] & bit)) continue;   // (the static class row holds valid & ready & constraints & platform & plugins)
+            if ((r.flags & RT_RES) && !(r.cpu <= cpu[n] && r.mem <= mem[n])) continue;
+            bool ok = true;
+            if (gset)
+                for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) {
+                    const u32 row = a.gs_row[g];
+                    if (a.gcnt[(size_t)a.rg_kind[row] * a.gstride + n] < a.rg_val[row]) ok = false;   // HasEnough, validate.go:24-52
+                }
+            if (ok && (r.flags & RT_PORTS))
+                for (u32 z = a.pset_off[r.pset]; z < a.pset_off[r.pset + 1]; ++z)
+                    if (wv::g_fresh64(a.portmap + (size_t)a.pset_ids[z] * Wn + w) & bit) ok = false;
+            if (ok && (r.flags & RT_MAXREP) && !((u64)(hi & 0xFFFFFFu) < r.maxrep)) ok = false;
+            if (!ok) continue;
+            const u32 tn = tot[n];
+            if (tn >> 20) a.blk->error = ERR_LEVEL_RANGE;   // (beyond the 20 bits the packed key has for the count)
+            wv::lds_min64(leafmin + lf, ((u64)hi << 32) | ((u64)tn << 12) | n);
+        }
+        // the next task's words are requested now: they have the rest of this task's turn to arrive
+        sc_n = sc_nn;
+        svc_n = svc_nn;
+        tree_n = tree_nn;
+        if (t + 1 < s.j1) ahead(sc_n, svc_n, tree_n);
+        {
+            const u32 t2 = t + 2 < s.j1 ? t + 2 : last;
+            sc_nn = a.rt[t2].sc;
+            svc_nn = a.rt[t2].svc;
+            tree_nn = p.ttree[t2];
+        }
+        wv::barrier();
+        // ---- wave 0: the sums up the tree, a level at a time from the deepest (a child's sum is complete before it is added), then the walk
+        if (tid < 64) {
+            for (u32 d = p.max_depth; d >= 1; --d) {
+                for (u32 i = lane; i < ntn; i += 64)
+                    if (l_depth[tbase + i] == d && tsum[i]) wv::lds_add32(tsum + l_parent[tbase + i], tsum[i]);
+                wv::wave_sync();
+                wv::lockstep();
+            }
+            if (lane == 0) {
+                bool hang = false;
+                res[set] = spread_walk(l_first + tbase, l_next + tbase, l_nchild + tbase, p.max_depth, ntn, leafmin, tsum, noroom, frames, &hang);
+                if (hang) a.blk->error = ERR_SPREAD_WALK;
+            }
+        }
+        wv::barrier();
+        const u64 gk = wv::lds_read64(res + set);
+        const u32 gn = gk == KEY_NONE ? R6_NONE : (u32)gk & 0xFFFu;
+        // ---- the owner of the node applies the placement (NodeInfo.addTask); everybody counts
+        if (gn == R6_NONE) {
+            if (tid == 0) {
+                a.inf_task[ni] = t;
+                a.inf_pos[ni] = nc;
+                a.out_node[t] = -1;
+            }
+            ++ni;
+        } else {
+            if ((gn & (SCAN_THREADS - 1u)) == tid) {
+                const u32 nd = gn, w = nd >> 6;
+                const u64 bit = 1ull << (nd & 63);
+                if (r.cpu) cpu[nd] -= r.cpu;
+                if (r.mem) mem[nd] -= r.mem;
+                if (gset)
+                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) a.gcnt[(size_t)a.rg_kind[a.gs_row[g]] * a.gstride + nd] -= a.rg_val[a.gs_row[g]];   // Claim
+                if (r.flags & RT_PORTS)
+                    for (u32 q = a.pset_off[r.pset]; q < a.pset_off[r.pset + 1]; ++q) wv::g_or64(a.portmap + (size_t)a.pset_ids[q] * Wn + w, bit);
+                if (!(r.flags & RT_UNCOUNTED)) {
+                    tot[nd] += 1;
+                    u32 hi = 0, entry = LIST_EMPTY;
+                    WV_UNROLL
+                    for (int q = 0; q < SCAN_NQ; ++q)
+                        if (tid + (u32)q * SCAN_THREADS == nd) { hi = hiq[q]; entry = enq[q]; }
+                    hi += 1u;
+                    if ((hi & 0xFFFFFFu) == 0) a.blk->error = ERR_GROUP_RANGE;
+                    s.hmat[(size_t)r.svc * N + nd] = hi;
+                    if (entry == LIST_EMPTY) {
+                        wv::g_or64(a.X + (size_t)r.svc * a.xs + w, bit);
+                        a.list_node[r.slot] = nd;
+                        a.list_svc[r.slot] = 1;
+                        a.list_fail[r.slot] = 0;
+                        s.emat[(size_t)r.svc * N + nd] = r.slot;
+                        entry = r.slot;
+                    } else
+                        a.list_svc[entry] = hi & 0xFFFFFFu;   // (the entry's count is the key half's low 24 bits)
+                    if (svc_n == r.svc) {   // the next task is of the same service: what it read of this node is a placement old
+                        WV_UNROLL
+                        for (int q = 0; q < SCAN_NQ; ++q)
+                            if (tid + (u32)q * SCAN_THREADS == nd) { hin[q] = hi; ein[q] = entry; }
+                    }
+                }
+                const int32_t prev = lastc[nd];
+                a.log_node[nc] = nd;
+                a.log_task[nc] = t;
+                a.log_prev[nc] = prev;
+                lastc[nd] = (int32_t)nc;
+                a.out_node[t] = (int32_t)nd;
+            }
+            ++nc;
+        }
+        // (no third barrier: a node's row and its matrix cells are read and written by its owner only; the per-tree words alternate)
+    }
+    for (u32 n = tid; n < N; n += SCAN_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    if (tid == 0) {
+        a.ctl->ncommit = nc;
+        a.ctl->ninf = ni;
+        a.blk->pos = s.j1;
+    }
+}
+#endif   // SWP_SCAN_SPREAD_KERNEL
+
+}  // namespace swpdev

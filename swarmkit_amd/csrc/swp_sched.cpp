@@ -469,7 +469,15 @@ struct TickProf {
 
 class Scheduler {
   public:
-    explicit Scheduler(swp_engine* e) : e_(e) { ck(swp_reset(e_, 0), "swp_reset"); }
+    explicit Scheduler(swp_engine* e) : e_(e) {
+        ck(swp_reset(e_, 0), "swp_reset");
+        const char* sp = std::getenv("SWP_SCHED_ONEOFF_SPREAD");   // (read once, here: swp_sched_create)
+        oneoff_spread_ = sp != nullptr && std::atoi(sp) != 0;
+    }
+    // SWP_SCHED_ONEOFF_SPREAD=1: one-off tasks with spread preferences stay in the tick's run of one-off tasks — ONE batch, whose spread
+    // segments decide them (swp.h, swp_schedule_batch) — instead of cutting the run at each of them for a group call of one task.
+    // Off by default: the call sequence is then the one tests/pyhost.py restates.
+    bool oneoff_spread_ = false;
     TickProf prof_;
 
     std::string scratch;   // result storage handed out through const char**
@@ -1382,6 +1390,28 @@ class Scheduler {
         std::vector<swp_task_desc> run_descs;   // Pipeline.SetTask once per task
         run.reserve(one_off.size());
         run_descs.reserve(one_off.size());
+        if (oneoff_spread_) {   // the whole run as ONE batch, the tasks with preferences in their places; refused at prepare: today's split
+            bool any_spread = false;
+            for (Item& it : one_off) {
+                try {
+                    run_descs.push_back(descOf(it.tmpl));
+                } catch (const Fail& f) {
+                    defer(it.first, it.second, f, decisions);
+                    continue;
+                }
+                run.push_back(std::move(it));
+                any_spread = any_spread || run_descs.back().spread_set != 0;
+            }
+            bool refused = !any_spread;   // (no such task: the loop below, which is today's)
+            if (any_spread) {
+                prof_.lap(3);
+                runOneOffs(run, run_descs, decisions, &refused);
+                if (!refused) return;
+            }
+            one_off = std::move(run);   // (the tasks whose descriptor failed have their decision line already)
+            run.clear();
+            run_descs.clear();
+        }
         for (Item& it : one_off) {
             swp_task_desc d;
             try {
@@ -2280,7 +2310,11 @@ class Scheduler {
         pushTouched();   // groups with generic reservations: the nodes' available lists after place()'s Claim
         prof_.lap(5);
     }
-    void runOneOffs(const std::vector<Item>& run, const std::vector<swp_task_desc>& descs, Decisions& decisions) {
+    // refused != nullptr (SWP_SCHED_ONEOFF_SPREAD: the run holds tasks with spread preferences): the batch goes through prepare / run /
+    // fetch, and a preparation the engine refuses as unsupported — its limits for such tasks, swp.h — sets *refused and leaves the
+    // run undecided and the engine untouched: the caller splits it
+    void runOneOffs(const std::vector<Item>& run, const std::vector<swp_task_desc>& descs, Decisions& decisions, bool* refused = nullptr) {
+        if (refused != nullptr) *refused = false;
         if (run.empty()) return;
         std::vector<int32_t> out(run.size(), -1);
         std::vector<uint32_t> hist(run.size() * SWP_NFILTERS, 0);
@@ -2289,13 +2323,18 @@ class Scheduler {
             if (descs[i].flags >> SWP_TASK_MOUNTS_SHIFT) with_mounts.push_back((uint32_t)i);
         std::vector<uint32_t> att(with_mounts.size() * SWP_MAX_MOUNTS, SWP_NO_VOLUME);
         try {
-            if (with_mounts.empty()) ck(swp_schedule_batch(e_, descs.data(), (uint32_t)descs.size(), out.data(), hist.data()), "swp_schedule_batch");
+            if (with_mounts.empty() && refused == nullptr) ck(swp_schedule_batch(e_, descs.data(), (uint32_t)descs.size(), out.data(), hist.data()), "swp_schedule_batch");
             else {   // the same in three steps: the batch is needed for its attachments
                 swp_batch* b = nullptr;
-                ck(swp_batch_prepare(e_, descs.data(), (uint32_t)descs.size(), &b), "swp_batch_prepare");
+                const int rp = swp_batch_prepare(e_, descs.data(), (uint32_t)descs.size(), &b);
+                if (rp == SWP_EUNSUPPORTED && refused != nullptr) {
+                    *refused = true;
+                    return;
+                }
+                ck(rp, "swp_batch_prepare");
                 int rc = swp_batch_run(e_, b);
                 if (rc == SWP_OK) rc = swp_batch_fetch(e_, b, out.data(), hist.data());
-                if (rc == SWP_OK) rc = swp_batch_attachments(e_, b, with_mounts.data(), (uint32_t)with_mounts.size(), att.data());
+                if (rc == SWP_OK && !with_mounts.empty()) rc = swp_batch_attachments(e_, b, with_mounts.data(), (uint32_t)with_mounts.size(), att.data());
                 if (rc != SWP_OK) engine_detail_ = std::string(swp_strerror(rc)) + ": " + swp_last_error(e_);
                 swp_batch_free(e_, b);
                 if (rc != SWP_OK) fail(rc, "swp_batch_run: " + engine_detail_);

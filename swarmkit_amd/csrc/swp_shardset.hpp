@@ -335,6 +335,9 @@ int batch_prepare(swp_engine* e, const swp_task_desc* tasks, uint32_t n, const u
     if (!out || (!tasks && n)) return SWP_EINVAL;
     *out = nullptr;
     if (S.broken) return broken_error(e);
+    // (a shard's engine would take a one-off task with spread preferences over ITS part of the nodeSet: the set refuses it as before)
+    for (uint32_t i = 0; i < (templates ? n_tmpl : n); ++i)
+        if (tasks[i].spread_set) return e->fail(SWP_EUNSUPPORTED, "%s %u has spread preferences: schedule it through swp_schedule_groups", templates ? "template" : "task", i);
     auto b = std::make_unique<swp_batch>();
     b->T = n;
     b->is_set = true;

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""What keeping one-off tasks with spread preferences in the tick's batch (SWP_SCHED_ONEOFF_SPREAD=1, csrc/swp_sched.cpp; the batch's
+spread segments, csrc/swp_scan_spread.hpp) gives a caller, against the host layer's default — the run of one-off tasks cut at every such
+task, each sent through swp_schedule_groups as a group of one — on the same box in the same run: one JSON line (and --out FILE, e.g.
+profiles/oneoff_spread.json).
+
+  (a) tick        swp_sched_tick over --tasks one-off tasks of --services services, every one with `spread=node.labels.zone`, on --nodes
+                  nodes: the knob off (today's path, the yardstick), then on; --runs fresh schedulers each, wall time of the tick alone,
+                  min / median / max and the spread of the runs. Both sides must decide every task alike.
+  (b) engine      the knob-on tick's device pass alone: the events around the spread segment (SWP_CFG_PROFILE: swp_stats ms_scan)
+                  and around the whole batch (ms_total), per task.
+  (c) tree price  the same descriptors through swp_schedule_batch with and without their preferences, engine events per task — at
+                  the shape of (a), where tasks without preferences go to the block resolver, and at --scan-shape (few services,
+                  more tasks than nodes), where the engine hands them to the scan resolver (k_scan / k_scanb): the counters say
+                  which resolver took how many.
+
+usage: python tools/bench_oneoff_spread.py [--tasks 20000] [--services 200] [--nodes 1000] [--zones 5] [--runs 3] [--out FILE]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from swarmkit_amd import abi  # noqa: E402
+from swarmkit_amd import host as swhost  # noqa: E402
+
+READY, RUNNING, PENDING, ASSIGNED = 2, 512, 64, 192
+KNOB = "SWP_SCHED_ONEOFF_SPREAD"
+
+
+def node_doc(i, zones):
+    return {"ID": "n%05d" % i, "Status": {"State": READY}, "Spec": {"Annotations": {"Labels": {"zone": "z%d" % (i % zones)}}},
+            "Description": {"Resources": {"NanoCPUs": 64 * 10**9, "MemoryBytes": 256 << 30}}}
+
+
+def task_doc(j, services, prefs=True):
+    spec = {"Resources": {"Reservations": {"NanoCPUs": 10**8, "MemoryBytes": 64 << 20}}}
+    if prefs:
+        spec["Placement"] = {"Preferences": [{"Spread": {"SpreadDescriptor": "node.labels.zone"}}]}
+    return {"ID": "t%06d" % j, "ServiceID": "svc%03d" % (j % services), "DesiredState": RUNNING, "Status": {"State": PENDING}, "Spec": spec}
+
+
+def loaded(a, knob, profile=False, tasks=True):
+    if knob:
+        os.environ[KNOB] = "1"
+    else:
+        os.environ.pop(KNOB, None)
+    s = swhost.HostScheduler(profile=profile)
+    for i in range(a.nodes):
+        s.create_node(node_doc(i, a.zones))
+    for k in range(a.services):
+        s.set_service("svc%03d" % k)
+    if tasks:
+        for j in range(a.tasks):
+            s.create_task(task_doc(j, a.services))
+    return s
+
+
+def one_tick(a, knob, profile=False):
+    s = loaded(a, knob, profile)
+    t = time.perf_counter()
+    d = s.tick()
+    ms = (time.perf_counter() - t) * 1e3
+    st = s.e.stats()
+    return ms, {x["ID"]: x["NodeID"] for x in d}, st
+
+
+def summary(v):
+    return {"runs": [round(x, 3) for x in v], "min": round(min(v), 3), "median": round(statistics.median(v), 3), "max": round(max(v), 3), "spread": round(max(v) - min(v), 3)}
+
+
+def batch_events(n_nodes, zones, services, n_tasks, prefs):
+    """one swp_schedule_batch over the descriptors on a fresh engine with SWP_CFG_PROFILE: the engine's own events"""
+    os.environ.pop(KNOB, None)
+    s = swhost.HostScheduler(profile=True)
+    for i in range(n_nodes):
+        s.create_node(node_doc(i, zones))
+    for k in range(services):
+        s.set_service("svc%03d" % k)
+    per = np.concatenate([s.task_desc(task_doc(k, services, prefs)) for k in range(services)])
+    descs = np.ascontiguousarray(per[np.arange(n_tasks) % services], dtype=abi.TASK_DTYPE)
+    out, _ = s.e.schedule_batch(descs)
+    st = s.e.stats()
+    return {"placed": int((out >= 0).sum()), "ms_total": round(st["ms_total"], 3), "ms_scan": round(st["ms_scan"], 3), "ms_resolve": round(st["ms_resolve"], 3),
+            "scan_tasks": st["scan_tasks"], "scan_batched_tasks": st["scan_batched_tasks"], "scan_launches": st["scan_launches"], "resolve_launches": st["resolve_launches"],
+            "us_per_task": round(st["ms_resolve"] * 1e3 / n_tasks, 3)}, out   # (ms_resolve: the resolvers' whole phase, the scan resolver's share — ms_scan — included)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tasks", type=int, default=20_000)
+    ap.add_argument("--services", type=int, default=200)
+    ap.add_argument("--nodes", type=int, default=1000)
+    ap.add_argument("--zones", type=int, default=5)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--scan-shape", default="10,500,20000", help="services,nodes,tasks of (c)'s second shape")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    os.environ["SWP_HOST"] = "cxx"
+    one_tick(argparse.Namespace(nodes=64, zones=a.zones, services=4, tasks=64), True)   # warm: modules, pools
+    off, on, want = [], [], None
+    for r in range(a.runs):
+        for knob in ((False, True) if r % 2 == 0 else (True, False)):
+            ms, dec, st = one_tick(a, knob)
+            (on if knob else off).append(ms)
+            if want is None:
+                want = dec
+            assert dec == want, "the two paths decide the tick differently"
+            if knob:
+                assert st["scan_tasks"] == a.tasks, st
+    ms, _, st = one_tick(a, True, profile=True)
+    engine = {"tick_ms_with_profile": round(ms, 3), "segment_ms": round(st["ms_scan"], 3), "batch_ms_total": round(st["ms_total"], 3),
+              "segment_us_per_task": round(st["ms_scan"] * 1e3 / a.tasks, 3), "scan_launches": st["scan_launches"], "scan_tasks": st["scan_tasks"]}
+    tree = {}
+    sv, nn, tt = (int(x) for x in a.scan_shape.split(","))
+    for name, (services, nodes, tasks) in (("tick_shape", (a.services, a.nodes, a.tasks)), ("scan_shape", (sv, nn, tt))):
+        with_p, out_p = batch_events(nodes, a.zones, services, tasks, True)
+        without, out_n = batch_events(nodes, a.zones, services, tasks, False)
+        tree[name] = {"services": services, "nodes": nodes, "tasks": tasks, "with_preferences": with_p, "without_preferences": without}
+    out = {"tool": "bench_oneoff_spread", "tasks": a.tasks, "services": a.services, "nodes": a.nodes, "zones": a.zones, "runs": a.runs,
+           "placed": sum(1 for v in want.values() if v),
+           "a_tick_ms": {"knob_off_parent_path": summary(off), "knob_on": summary(on), "off_over_on_median": round(statistics.median(off) / statistics.median(on), 2)},
+           "b_engine_knob_on": engine, "c_tree_price": tree}
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
