@@ -315,13 +315,22 @@ typedef struct {
  * a heap of one per leaf, scheduleNTasksOnSubtree (scheduler.go:772-825) with n = 1 at the root — decided on the device between the
  * tasks in front of it and behind it (a batch's spread segments, csrc/swp_scan_spread.hpp), its Explain row the plain first-fail
  * histogram like any other task's. Limits, checked when the batch is prepared, on the nodeSet it is prepared for:
- *   - at most 4 096 node slots;
- *   - the node rows (24 bytes a slot) and the trees of the batch's spread sets — 32 bytes per branch of the largest tree, 20 per
- *     branch of all of them, 32 per level — fit 160 KiB - 512 bytes of LDS (4 096 slots leave room for some 1 200 branches);
+ *   - every spread segment of the batch (a task with preferences, the tasks with preferences behind it and the tasks without that
+ *     stand between them or fewer than 64 behind the last) can use at most 4 096 nodes: on a nodeSet of at most 4 096 node slots
+ *     that is every segment; on a larger one it is the UNION of the static class rows its tasks name — the nodes that are READY and
+ *     pass the Constraint, Platform and Plugin filters of one of them: services constrained to a labelled pool of a large cluster
+ *     (the compact instance; the nodes outside the union still weigh on the tree with their tasks of the service). The class rows
+ *     exist on the device only: the preparation computes them and probes every segment. A segment with one unconstrained task has
+ *     the whole nodeSet as its union;
+ *   - the node rows (24 bytes a slot, or a node of the largest union) and the trees of the batch's spread sets — 32 bytes per branch
+ *     of the largest tree, 20 per branch of all of them, 32 per level — fit 160 KiB - 512 bytes of LDS (4 096 nodes leave room for
+ *     some 1 200 branches);
  *   - no exception entry beyond the scan resolver's keys (256 recorded failures, 2^24 tasks of a service on a node).
  * Outside them, for a task that has cluster mounts as well (SWP_TASK_MOUNTS), on a shard set and in the shard / rank protocols
  * (swp_shard_*), the refusal is SWP_EUNSUPPORTED as before — the message names the limit — with engine and mirror untouched: such a task
  * goes through swp_schedule_groups as a group of one. swp_fit_pairs* refuse templates with preferences as before.
+ * On a nodeSet beyond 4 096 slots swp_batch_run checks the unions again before its first placing launch — a node upserted since the
+ * preparation is sent to the device first — and refuses in the same way, rows and mirror untouched.
  * (swp_stats: a spread segment counts as a stretch of the scan resolver — scan_launches, scan_tasks, ms_scan.) */
 int swp_schedule_batch(swp_engine*, const swp_task_desc* tasks, uint32_t n_tasks,
                        int32_t* out_node, uint32_t* out_fail_hist /* [n_tasks][SWP_NFILTERS] */);

@@ -476,6 +476,12 @@ struct swp_batch {
     std::vector<uint32_t> sp_sets, sp_tree;
     SpreadTrees sp_trees;
     DevBuf d_sp_tree, d_sp_off, d_sp_par, d_sp_first, d_sp_next, d_sp_nch, d_sp_depth, d_sp_leaf;
+    // a nodeSet beyond the scan resolver's node count: the spread segments run compact, each over the union of its tasks' class rows
+    // (k_scan_spread<.., true>). sp_pair[task] = its (service, tree) pair, whose leaf sums over the nodes outside a segment's union
+    // k_spread_base computes per segment; sp_nc[i] = the union's node count of the i-th spread segment, as the last probe read it
+    bool sp_compact = false;
+    std::vector<uint32_t> sp_pair, sp_pair_svc, sp_pair_tree, sp_nc;
+    DevBuf d_sp_pair, d_sp_psvc, d_sp_ptree, d_sp_base, d_sp_cnc;
     bool wide_keys = false;                // an exception entry beyond the 8 + 24 bit keys of k_waterfill and the scan resolver: the block resolver decides alone
     DevBuf d_wf;                           // k_waterfill scratch: [3][n_nodes] u32
     // the streamed run (swp_batch_run_streamed, swp_publish.hpp): the host-visible block k_publish writes — the mark counter on a line
@@ -1088,8 +1094,7 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
         if (d.spread_set >= e->spread_sets.size()) return e->fail(SWP_EINVAL, "task %u references an unknown spread set", i);
         // a one-off task with spread preferences: a spread segment decides it (swp_scan_spread.hpp), within that kernel's limits
         if (d.spread_set && !weights) {
-            if (e->n_nodes > scan_max_nodes())
-                return e->fail(SWP_EUNSUPPORTED, "task %u has spread preferences: schedule it through swp_schedule_groups (a batch takes them on at most %u node slots, this nodeSet has %u)", i, scan_max_nodes(), e->n_nodes);
+            // (a nodeSet beyond the scan resolver's node count: decided by the probe of the segments' unions, spread_probe)
             if (d.flags >> SWP_TASK_MOUNTS_SHIFT)
                 return e->fail(SWP_EUNSUPPORTED, "task %u has spread preferences: schedule it through swp_schedule_groups (a batch takes none that also has cluster mounts)", i);
         }
@@ -1399,6 +1404,7 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
     // (swp_rounds.hpp spread_segments). The trees are built once here for the limit — the largest tree's words next to the node rows
     // in the kernel's LDS — and again from the mirror when the batch runs.
     b->has_spread = false;
+    b->sp_compact = false;
     b->sp_sets.clear();
     b->sp_tree.clear();
     if (!weights) {
@@ -1421,8 +1427,27 @@ int build_batch(swp_engine* e, const swp_task_desc* descs, uint32_t T, swp_batch
             }
             b->sp_tree[i] = it->second;
         }
+        // beyond the scan resolver's node count the segments run compact: the pairs, in the order their first task appears
+        b->sp_compact = e->n_nodes > scan_max_nodes();
+        b->sp_pair.clear();
+        b->sp_pair_svc.clear();
+        b->sp_pair_tree.clear();
+        if (b->sp_compact) {
+            std::unordered_map<uint64_t, uint32_t> pair_local;
+            b->sp_pair.assign(T, 0);
+            for (uint32_t i = 0; i < T; ++i) {
+                const uint64_t k = ((uint64_t)b->rt[i].svc << 32) | b->sp_tree[i];
+                auto it = pair_local.find(k);
+                if (it == pair_local.end()) {
+                    it = pair_local.emplace(k, (uint32_t)b->sp_pair_svc.size()).first;
+                    b->sp_pair_svc.push_back(b->rt[i].svc);
+                    b->sp_pair_tree.push_back(b->sp_tree[i]);
+                }
+                b->sp_pair[i] = it->second;
+            }
+        }
         build_spread_trees(e, b->sp_sets, &b->sp_trees);
-        if (scan_spread_lds_size(e->n_nodes, b->sp_trees.max_ntn, b->sp_trees.max_depth, (uint32_t)b->sp_sets.size(), b->sp_trees.tree_off.back()) > R6_LDS_BUDGET)
+        if (!b->sp_compact && scan_spread_lds_size(e->n_nodes, b->sp_trees.max_ntn, b->sp_trees.max_depth, (uint32_t)b->sp_sets.size(), b->sp_trees.tree_off.back()) > R6_LDS_BUDGET)
             return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (%u node slots and trees of %u branches, the largest of %u over %u levels, exceed the spread kernel's LDS)",
                            e->n_nodes, b->sp_trees.tree_off.back(), b->sp_trees.max_ntn, b->sp_trees.max_depth);
         std::vector<swp_batch::Seg> cut;
@@ -2177,12 +2202,73 @@ int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra
     return SWP_OK;
 }
 
+// A batch with spread segments on a nodeSet beyond the scan resolver's node count: the probe of EVERY spread segment — k_scan_mark +
+// k_scan_union over its tasks' class rows as run_classes left them (the caller ran it), each count into a word of its own, all read
+// back in one copy — and the limit: a union of at most scan_max_nodes() nodes whose rows fit the spread kernel's LDS next to the trees
+// (b->sp_trees, built by the caller; the base sums take none: a register a thread, swp_scan_spread.hpp). Refuses with nothing written
+// but the batch's own probe buffers. The unions themselves are built again, segment by segment, when the segments run (the scan
+// stretches in between share the buffers).
+int spread_probe(swp_engine* e, swp_batch* b) {
+    uint32_t n_seg = 0;
+    for (const swp_batch::Seg& sg : b->segs) n_seg += sg.spread ? 1u : 0u;
+    b->sp_nc.assign(n_seg, 0);
+    if (!n_seg) return SWP_OK;
+    HIPCHECK(e, b->d_sp_cnc.reserve((size_t)n_seg * 4));
+    ScanArgs sa{};
+    sa.a.n_nodes = e->n_nodes;
+    sa.a.n_words = n_words_of(e->n_nodes);
+    sa.a.rt = b->d_rt.as<RTask>();
+    sa.a.sc = b->d_sc.as<u64>();
+    sa.n_svc = b->n_svc;
+    sa.n_sc = b->n_sc;
+    if (int rc = scan_compact_bufs(e, b, &sa)) return rc;
+    uint32_t k = 0;
+    for (const swp_batch::Seg& sg : b->segs) {
+        if (!sg.spread) continue;
+        sa.j0 = sg.j0;
+        sa.j1 = sg.j0 + sg.n;
+        sa.cnc = b->d_sp_cnc.as<uint32_t>() + k++;
+        const hipError_t r = launch_scan_probe(sa, e->stream);   // (zeroes cused in front of the marks)
+        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan_union launch: %s", hipGetErrorString(r));
+    }
+    HIPCHECK(e, hipMemcpyAsync(b->sp_nc.data(), b->d_sp_cnc.p, (size_t)n_seg * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    const SpreadTrees& t = b->sp_trees;
+    k = 0;
+    for (const swp_batch::Seg& sg : b->segs) {
+        if (!sg.spread) continue;
+        const uint32_t nc = b->sp_nc[k++];
+        if (nc > scan_max_nodes())
+            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (a batch takes them where the nodes its segment's tasks can use number at most %u: the union of the class rows of segment %u, tasks [%u, %u), has %u of this nodeSet's %u)",
+                           scan_max_nodes(), k - 1, sg.j0, sg.j0 + sg.n, nc, e->n_nodes);
+        if (scan_spread_lds_size(nc, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) > R6_LDS_BUDGET)
+            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (the %u nodes of the union of segment %u, tasks [%u, %u), and trees of %u branches, the largest of %u over %u levels, exceed the spread kernel's LDS; at most %u nodes in any case)",
+                           nc, k - 1, sg.j0, sg.j0 + sg.n, t.tree_off.back(), t.max_ntn, t.max_depth, scan_max_nodes());
+    }
+    return SWP_OK;
+}
+
+// ... at swp_batch_prepare, behind the node flush and the batch's upload: the class rows exist only on the device
+int spread_prepare_probe(swp_engine* e, swp_batch* b) {
+    if (!b->T || !e->n_nodes) return SWP_OK;
+    if (int rc = run_classes(e, b)) return rc;
+    return spread_probe(e, b);
+}
+
 // A batch with spread segments, once per run and before its first launch: the trees of its spread sets from the nodeSet as the mirror
-// holds it NOW (the batch may have been prepared before a label moved), the limit checked again, the tables uploaded.
+// holds it NOW (the batch may have been prepared before a label moved), the limit checked again — compact: by the probe, behind
+// batch_begin's run_classes —, the tables uploaded.
 int spread_tables(swp_engine* e, swp_batch* b) {
     build_spread_trees(e, b->sp_sets, &b->sp_trees);
     const SpreadTrees& t = b->sp_trees;
-    if (e->n_nodes > scan_max_nodes() || scan_spread_lds_size(e->n_nodes, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) > R6_LDS_BUDGET)
+    if (b->sp_compact) {
+        int rc;
+        if ((rc = spread_probe(e, b))) return rc;
+        if ((rc = upload(e, b->d_sp_pair, b->sp_pair))) return rc;
+        if ((rc = upload(e, b->d_sp_psvc, b->sp_pair_svc))) return rc;
+        if ((rc = upload(e, b->d_sp_ptree, b->sp_pair_tree))) return rc;
+        HIPCHECK(e, b->d_sp_base.reserve(std::max<size_t>((size_t)b->sp_pair_svc.size() * t.max_ntn, 1) * 4));
+    } else if (e->n_nodes > scan_max_nodes() || scan_spread_lds_size(e->n_nodes, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) > R6_LDS_BUDGET)
         return e->fail(SWP_EUNSUPPORTED, "the batch has tasks with spread preferences: %u node slots and a tree of %u branches over %u levels exceed the spread kernel's LDS (swp_schedule_groups takes them)",
                        e->n_nodes, t.max_ntn, t.max_depth);
     int rc;
@@ -2201,7 +2287,7 @@ int spread_tables(swp_engine* e, swp_batch* b) {
 // and the logs come out as the scan resolver leaves them; the block resolver's bitmaps are NOT rebuilt here — a stretch of rounds
 // behind the segment builds them from the node rows when it begins (stretch_begin), a k_waterfill run reads none — so a batch that is
 // all spread segments never meets the block resolver's limit on the nodes' task-count spread. Streamed: a publish behind the segment.
-int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_t j1) {
+int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_t j1, uint32_t seg_index) {
     hipStream_t st = e->stream;
     R6Args ra{};
     if (int rc = r6_args_for(e, b, run.largest(), run.task_rows, run.knobs, &ra)) return rc;
@@ -2212,10 +2298,22 @@ int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_
     sa.j1 = j1;
     sa.n_svc = b->n_svc;
     sa.n_sc = b->n_sc;
-    HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * e->n_nodes * 4));
-    HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * e->n_nodes * 4));
+    // compact: the union of the segment's class rows into the batch's compact buffers (shared with the scan stretches: built again
+    // here), its node count as spread_tables' probe of this run read it — the class rows do not move inside a run
+    const bool cm = b->sp_compact;
+    const uint32_t n_c = cm ? b->sp_nc[seg_index] : 0u;
+    const size_t cols = cm ? std::max<uint32_t>(n_c, 1u) : e->n_nodes;
+    HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * cols * 4));
+    HIPCHECK(e, b->d_emat.reserve((size_t)b->n_svc * cols * 4));
     sa.hmat = b->d_hmat.as<uint32_t>();
     sa.emat = b->d_emat.as<uint32_t>();
+    if (cm) {
+        if (int rc = scan_compact_bufs(e, b, &sa)) return rc;
+        sa.n_c = n_c;
+        sp.tpair = b->d_sp_pair.as<uint32_t>();
+        sp.base = b->d_sp_base.as<uint32_t>();
+        sp.n_pairs = (uint32_t)b->sp_pair_svc.size();
+    }
     sp.ttree = b->d_sp_tree.as<uint32_t>();
     sp.tree_off = b->d_sp_off.as<uint32_t>();
     sp.tn_parent = b->d_sp_par.as<uint32_t>();
@@ -2233,8 +2331,15 @@ int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_
         if (int rc = grow_events(e, e->ev_scan, (size_t)e->ev_scan_used + 2)) return rc;
         HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used], st));
     }
-    hipError_t r = launch_scan_matrices(sa, st);
-    if (r == hipSuccess) r = launch_scan_spread(sp, st, e->device);
+    hipError_t r;
+    if (!cm) {
+        r = launch_scan_matrices(sa, st);
+        if (r == hipSuccess) r = launch_scan_spread(sp, st, e->device);
+    } else {
+        r = launch_scan_probe(sa, st);
+        if (r == hipSuccess) r = launch_scan_matrices_compact(sa, st);
+        if (r == hipSuccess) r = launch_scan_spread_compact(sp, b->d_sp_psvc.as<uint32_t>(), b->d_sp_ptree.as<uint32_t>(), b->d_sp_base.as<uint32_t>(), st, e->device);
+    }
     if (run.prof) {
         HIPCHECK(e, hipEventRecord(e->ev_scan[e->ev_scan_used + 1], st));
         e->ev_scan_used += 2;
@@ -2250,7 +2355,10 @@ int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_
     if (hb.error == ERR_LEVEL_RANGE) return e->fail(SWP_ERANGE, "a node holds 2^20 tasks or more: beyond the scan resolver's packed key");
     if (hb.error != ERR_NONE) return e->fail(SWP_EHIP, "k_scan_spread: the walk of a task did not end within its bound (error %u)", hb.error);
     if (hb.pos != j1) return e->fail(SWP_EHIP, "k_scan_spread stopped at task %u of [%u, %u)", hb.pos, j0, j1);
-    if (run.knobs.dbg & 16) fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u): trees of at most %u branches over %u levels\n", j0, j1, sp.max_ntn, sp.max_depth);
+    if (run.knobs.dbg & 16) {
+        if (cm) fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u) over a union of %u of %u nodes, %u (service, tree) pairs: trees of at most %u branches over %u levels\n", j0, j1, n_c, e->n_nodes, sp.n_pairs, sp.max_ntn, sp.max_depth);
+        else fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u): trees of at most %u branches over %u levels\n", j0, j1, sp.max_ntn, sp.max_depth);
+    }
     return SWP_OK;
 }
 
@@ -2467,17 +2575,21 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
     e->ev_scan_used = 0;
     e->scan_tasks_batch = e->scan_stretches_batch = e->scan_batched_batch = e->scan_skipped_batch = 0;
 
-    int rc = batch_begin(e, b);
-    if (rc) return rc;
+    int rc;
+    // compact spread segments are limited by what the class rows say NOW, and their trees are built from the mirror as it is now: a
+    // node upserted since the preparation (a label moved into the pool) goes to the device first, as the next preparation would send it
+    if (b->sp_compact && e->dev_static_dirty && (rc = flush_nodes(e))) return rc;
+    if ((rc = batch_begin(e, b))) return rc;
     if (run.prof) HIPCHECK(e, hipEventRecord(e->ev[1], st));
     if ((rc = r6_run_plan(e, b, &run))) return rc;
     if (b->has_spread && (rc = spread_tables(e, b))) return rc;
     if (b->segs.empty()) rc = run_stretch(e, b, run, 0, T);
     else {
         HIPCHECK(e, b->d_wf.reserve((size_t)3 * N * 4));
+        uint32_t spread_seen = 0;
         for (const swp_batch::Seg& sg : b->segs) {
             if (sg.spread) {
-                if ((rc = spread_segment(e, b, run, sg.j0, sg.j0 + sg.n))) break;
+                if ((rc = spread_segment(e, b, run, sg.j0, sg.j0 + sg.n, spread_seen++))) break;
                 continue;
             }
             if (!sg.run) {
@@ -3865,6 +3977,7 @@ int swp_batch_prepare(swp_engine* e, const swp_task_desc* tasks, uint32_t n_task
     const auto t1 = std::chrono::steady_clock::now();
     if (e->dev_static_dirty && (rc = flush_nodes(e))) return rc;
     if (n_tasks && e->n_nodes && (rc = upload_batch(e, b.get()))) return rc;
+    if (b->sp_compact && (rc = spread_prepare_probe(e, b.get()))) return rc;
     if (dbg) {
         const auto t2 = std::chrono::steady_clock::now();
         fprintf(stderr, "[swp] swp_batch_prepare %u tasks: build %.2f ms, upload %.2f ms\n", n_tasks, std::chrono::duration<double, std::milli>(t1 - t0).count(),
@@ -3889,6 +4002,7 @@ int swp_batch_prepare_templates(swp_engine* e, const swp_task_desc* templates, u
     if (e->dev_static_dirty && (rc = flush_nodes(e))) return rc;
     sp.next("prepare_templates: upload_batch");
     if (n_tasks && e->n_nodes && (rc = upload_batch(e, b.get()))) return rc;
+    if (b->sp_compact && (rc = spread_prepare_probe(e, b.get()))) return rc;
     b->n_nodes_prepared = e->n_nodes;
     *out = b.release();
     return SWP_OK;

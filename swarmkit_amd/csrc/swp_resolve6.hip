@@ -204,6 +204,13 @@ hipError_t launch_scan_matrices(const ScanArgs& s, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ... over the union's n_c columns, behind launch_scan_probe (the compact spread instance; n_c may be 0: nothing to fill)
+hipError_t launch_scan_matrices_compact(const ScanArgs& s, hipStream_t st) {
+    hipLaunchKernelGGL(k_scan_fill_c, dim3(1024), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(k_scan_lists_c, dim3(64, s.n_svc), dim3(256), 0, st, s);
+    return hipGetLastError();
+}
+
 // ---- the compact instance: a cluster beyond SCAN_MAXN nodes, a stretch whose class rows' union is not ----
 // the probe: which class rows the tasks [j0, j1) name, their union, its node count (*s.cnc: the caller reads it), prefix sums and map
 hipError_t launch_scan_probe(const ScanArgs& s, hipStream_t st) {

@@ -30,4 +30,27 @@ hipError_t launch_scan_spread(const SpreadArgs& p, hipStream_t st, int dev) {
     }
 }
 
+// ---- the compact instance: a nodeSet beyond SCAN_MAXN slots, a segment whose class rows' union is not
+template <int NQ>
+static hipError_t launch_scan_spread_c_as(const SpreadArgs& p, size_t lds, hipStream_t st, int dev) {
+    hipError_t r;
+    if (lds > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(&k_scan_spread<NQ, true>), dev)) != hipSuccess) return r;
+    hipLaunchKernelGGL((k_scan_spread<NQ, true>), dim3(1), dim3(SCAN_THREADS), lds, st, p);
+    return hipGetLastError();
+}
+// behind launch_scan_probe of [p.s.j0, p.s.j1) (p.s.n_c as read from it, 0 included: every task is left without a node) and
+// launch_scan_matrices_compact: the pairs' base sums from the lists as they are, then the tasks one after the other
+hipError_t launch_scan_spread_compact(const SpreadArgs& p, const uint32_t* pair_svc, const uint32_t* pair_tree, uint32_t* base, hipStream_t st, int dev) {
+    const size_t lds = scan_lds_sp(p.s.n_c, p.max_ntn, p.max_depth, p.n_trees, p.tot_ntn);
+    if (p.s.n_c > SCAN_MAXN || p.n_pairs == 0 || lds > (size_t)160 * 1024 - 512) return hipErrorInvalidValue;
+    hipError_t r = hipMemsetAsync(base, 0, (size_t)p.n_pairs * p.max_ntn * 4, st);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(k_spread_base, dim3(64, p.n_pairs), dim3(256), 0, st, p, pair_svc, pair_tree, base);
+    switch (scan_nq(p.s.n_c)) {
+        case 1: return launch_scan_spread_c_as<1>(p, lds, st, dev);
+        case 2: return launch_scan_spread_c_as<2>(p, lds, st, dev);
+        default: return launch_scan_spread_c_as<4>(p, lds, st, dev);
+    }
+}
+
 }  // namespace swpdev

@@ -21,6 +21,8 @@
 //
 // Written against swp_wave.hpp only (tests/emu/emu_scan_spread.cpp runs it on CPU fibers against a sequential model).
 #pragma once
+#include <type_traits>
+
 #include "swp_scan.hpp"
 
 namespace swpdev {
@@ -39,6 +41,10 @@ struct SpreadArgs {
     const u32* leaf_of_node;   // [trees][n_nodes] local index of the node's leaf, 0xFFFFFFFF: the node is not in the nodeSet
     u32 max_ntn, max_depth; // over the batch's trees: tree nodes of the largest, levels of the deepest
     u32 n_trees, tot_ntn;   // trees; tree nodes of all of them (tree_off[n_trees]): the tables' length — the kernel keeps them in LDS
+    // the compact instance (k_scan_spread<.., true>, below) only; null / 0 for the plain one
+    const u32* tpair;       // [tasks of the batch] the task's (service, tree) pair
+    const u32* base;        // [n_pairs][max_ntn] a pair's leaf sums over the nodes OUTSIDE the segment's union (k_spread_base)
+    u32 n_pairs;
 };
 
 struct SpFrame {   // one invocation of scheduleNTasksOnSubtree that went past the leaf test (scheduler.go:784-822)
@@ -52,6 +58,32 @@ inline __host__ __device__ size_t scan_lds_sp(u32 n_nodes, u32 max_ntn, u32 max_
 }
 
 #ifdef SWP_SCAN_SPREAD_KERNEL
+// The compact instance's base sums. nodeSet.tree adds a node's count of the service to every branch on its path whether the node passes
+// the filters or not, so a node outside the segment's union — never picked, never changed inside the segment — still weighs on the
+// walk: with a constant, per (service, tree) pair. base[pair][leaf] = the sum of list_svc over the service's list entries whose node lies
+// outside the union (cu bit clear) and has a leaf in the pair's tree. base zeroed before; grid (list entries / 256, pairs), as
+// k_scan_lists_c; from the lists as they are when the segment begins. A pair of tree 0 (one leaf: its sum is never read) is left at 0.
+// (many workgroups add to a pair's row. On the CPU fibers one thread runs at a time: a plain add, as r6_count32)
+#if defined(__HIPCC__)
+WV_DEV void sp_add32(u32* p, u32 v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#else
+inline void sp_add32(u32* p, u32 v) { *p += v; }
+#endif
+WV_KERNEL(256) void k_spread_base(SpreadArgs p, const u32* pair_svc, const u32* pair_tree, u32* base) {
+    const u32 pr = wv::block_y(), svc = pair_svc[pr], tree = pair_tree[pr];
+    if (tree == 0) return;
+    const ScanArgs& s = p.s;
+    const u32 ntn = p.tree_off[tree + 1] - p.tree_off[tree];
+    const u32 e0 = s.a.list_off[svc], e1 = s.a.list_off[svc + 1];
+    for (u32 e = e0 + wv::block() * 256 + wv::tid(); e < e1; e += 256u * 64u) {
+        const u32 n = s.a.list_node[e];
+        if (n == LIST_EMPTY || ((s.cu[n >> 6] >> (n & 63)) & 1ull)) continue;   // (inside the union: the kernel adds it, task by task)
+        const u32 lf = p.leaf_of_node[(size_t)tree * s.a.n_nodes + n], sv = s.a.list_svc[e];
+        if (lf >= ntn || sv == 0) continue;   // (0xFFFFFFFF: the node is not in the nodeSet)
+        sp_add32(base + (size_t)pr * p.max_ntn + lf, sv);
+    }
+}
+
 // scheduleNTasksOnSubtree with one task, up to the first leaf that holds a node: its key (KEY_NONE: no leaf does). One thread.
 // tn_first / tn_next / tn_nchild: the tree's own rows of the tables (local indices); max_depth: the frames there are
 WV_DEV u64 spread_walk(const u32* tn_first, const u32* tn_next, const u32* tn_nchild, u32 max_depth, u32 ntn, const u64* leafmin, const u32* tsum, u32* noroom, SpFrame* st, bool* hang) {
@@ -131,11 +163,15 @@ WV_DEV u64 spread_walk(const u32* tn_first, const u32* tn_next, const u32* tn_nc
     return KEY_NONE;
 }
 
-template <int SCAN_NQ>
+// SCAN_CM: the COMPACT instance (a nodeSet beyond SCAN_MAXN slots, a segment whose class rows' union is not; swp_scan.hpp) — N is the
+// union's node count, the LDS rows, the matrices and the key's low 12 bits carry the compact index c (cmap ascending: the lowest c among
+// equal keys is the lowest node), everything that is indexed by node in global memory or leaves the kernel the node behind it (`real`, in
+// registers for the segment), and a task's leaf sums start from its pair's base row (k_spread_base) instead of 0. false: the plain code.
+template <int SCAN_NQ, bool SCAN_CM = false>
 WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
     const ScanArgs& s = p.s;
     const R6Args& a = s.a;
-    const u32 tid = wv::tid(), lane = wv::lane(), N = a.n_nodes, Wn = a.n_words, M = p.max_ntn;
+    const u32 tid = wv::tid(), lane = wv::lane(), N = SCAN_CM ? s.n_c : a.n_nodes, Wn = a.n_words, M = p.max_ntn;
     unsigned char* l = reinterpret_cast<unsigned char*>(wv::lds());
     i64* cpu = reinterpret_cast<i64*>(l);
     i64* mem = cpu + N;
@@ -153,8 +189,22 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
     u32* l_nchild = l_next + p.tot_ntn;
     u32* l_depth = l_nchild + p.tot_ntn;
     if (a.blk->error != ERR_NONE) return;
-    for (u32 n = tid; n < N; n += SCAN_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
-    for (u32 i = tid; i < 2 * M; i += SCAN_THREADS) { lmin[i] = KEY_NONE; lsum[i] = 0; lnor[i] = 0; }
+    const u32 first = s.j0 < s.j1 ? s.j0 : 0u, last = s.j0 < s.j1 ? s.j1 - 1u : 0u;   // (reads beyond the stretch are clamped to its last task and never used)
+    const u32 second = s.j0 + 1u < s.j1 ? s.j0 + 1u : last;
+    u32 real[SCAN_NQ];   // SCAN_CM: the nodes behind this thread's rows, fixed for the segment
+    if (!SCAN_CM) {
+        for (u32 n = tid; n < N; n += SCAN_THREADS) { cpu[n] = a.cpu[n]; mem[n] = a.mem[n]; tot[n] = a.total[n]; lastc[n] = a.last[n]; }
+        for (u32 i = tid; i < 2 * M; i += SCAN_THREADS) { lmin[i] = KEY_NONE; lsum[i] = 0; lnor[i] = 0; }
+    } else {
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS, m = n < N ? s.cmap[n] : 0u;
+            real[q] = m;
+            if (n < N) { cpu[n] = a.cpu[m]; mem[n] = a.mem[m]; tot[n] = a.total[m]; lastc[n] = a.last[m]; }
+        }
+        const u32* b0 = p.base + (size_t)p.tpair[first] * M;   // the first task's set starts from its pair's base sums
+        for (u32 i = tid; i < 2 * M; i += SCAN_THREADS) { lmin[i] = KEY_NONE; lsum[i] = i < M ? b0[i] : 0u; lnor[i] = 0; }
+    }
     for (u32 i = tid; i <= p.n_trees; i += SCAN_THREADS) l_off[i] = p.tree_off[i];
     for (u32 i = tid; i < p.tot_ntn; i += SCAN_THREADS) {
         l_parent[i] = p.tn_parent[i]; l_first[i] = p.tn_first[i]; l_next[i] = p.tn_next[i]; l_nchild[i] = p.tn_nchild[i]; l_depth[i] = p.tn_depth[i];
@@ -162,8 +212,8 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
     u32 present = 0;   // bit q: this thread's q-th node is in the nodeSet
     WV_UNROLL
     for (int q = 0; q < SCAN_NQ; ++q) {
-        const u32 n = tid + (u32)q * SCAN_THREADS;
-        if (n < N && ((a.valid[n >> 6] >> (n & 63)) & 1ull)) present |= 1u << q;
+        const u32 n = tid + (u32)q * SCAN_THREADS, m = SCAN_CM ? real[q] : n;
+        if (n < N && ((a.valid[m >> 6] >> (m & 63)) & 1ull)) present |= 1u << q;
     }
     u32 nc = a.ctl->ncommit, ni = a.ctl->ninf;
     // What a task reads from global memory is requested AHEAD, as k_scan does: the three words that say where the rest lies — its
@@ -171,54 +221,82 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
     // half, the list entry and the leaf of each of this thread's nodes — one task ahead. A task's turn then starts with everything in
     // registers. The one value the task in between can change, the key half (and the entry) of the node it takes, is corrected by
     // that node's owner.
-    const u32 first = s.j0 < s.j1 ? s.j0 : 0u, last = s.j0 < s.j1 ? s.j1 - 1u : 0u;   // (reads beyond the stretch are clamped to its last task and never used)
-    const u32 second = s.j0 + 1u < s.j1 ? s.j0 + 1u : last;
     u32 sc_n = a.rt[first].sc, svc_n = a.rt[first].svc, tree_n = p.ttree[first];
     u32 sc_nn = a.rt[second].sc, svc_nn = a.rt[second].svc, tree_nn = p.ttree[second];
-    u64 scn[SCAN_NQ];
+    // (SCAN_CM, four nodes a thread: the register file is the limit — the class word is kept as the 32-bit half that holds the node's bit)
+    typename std::conditional<SCAN_CM, u32, u64>::type scn[SCAN_NQ];
     u32 hin[SCAN_NQ], ein[SCAN_NQ], lfn[SCAN_NQ];
+    const u32* sc32 = reinterpret_cast<const u32*>(a.sc);
     auto ahead = [&](u32 sc_, u32 svc_, u32 tree_) {   // this thread's nodes for the task with this class row, service and tree
         WV_UNROLL
         for (int q = 0; q < SCAN_NQ; ++q) {
-            const u32 n = tid + (u32)q * SCAN_THREADS;
+            const u32 n = tid + (u32)q * SCAN_THREADS, m = SCAN_CM ? real[q] : n;
             const bool in = (present >> q) & 1u;
-            scn[q] = in ? a.sc[(size_t)sc_ * Wn + (n >> 6)] : 0ull;
+            if (SCAN_CM) scn[q] = in ? sc32[(size_t)sc_ * Wn * 2u + (m >> 5)] : 0u;
+            else scn[q] = in ? a.sc[(size_t)sc_ * Wn + (m >> 6)] : 0ull;
             hin[q] = in ? s.hmat[(size_t)svc_ * N + n] : 0u;
-            ein[q] = in ? s.emat[(size_t)svc_ * N + n] : LIST_EMPTY;
-            lfn[q] = in ? p.leaf_of_node[(size_t)tree_ * N + n] : LIST_EMPTY;
+            if (!SCAN_CM) ein[q] = in ? s.emat[(size_t)svc_ * N + n] : LIST_EMPTY;
+            lfn[q] = in ? p.leaf_of_node[(size_t)tree_ * a.n_nodes + m] : LIST_EMPTY;
+        }
+    };
+    // SCAN_CM: a node's list entry is read by the owner of the pick only, behind the task's second barrier — it is requested at the END of
+    // the turn before (it has a whole turn to arrive), so that no copy of the current task's entries has to be kept while the next
+    // task's are under way: four nodes a thread leave no registers for one.
+    auto ahead_entries = [&](u32 svc_) {
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS;
+            ein[q] = ((present >> q) & 1u) ? s.emat[(size_t)svc_ * N + n] : LIST_EMPTY;
         }
     };
     ahead(sc_n, svc_n, tree_n);
+    if (SCAN_CM) ahead_entries(svc_n);
+    // SCAN_CM: the base row of the NEXT task's pair is stored where that task's set is cleared, in front of this task's first barrier.
+    // It is requested a task ahead of the store (bn: this thread's word of the row, i = tid — a tree of more than SCAN_THREADS branches
+    // reads the words beyond from global memory in place), and the pair that says which row a task before that (pr_nn), with sc / svc / tree.
+    u32 bn = 0, pr_nn = 0;
+    if (SCAN_CM) {
+        bn = tid < M ? p.base[(size_t)p.tpair[second] * M + tid] : 0u;   // the row of task j0 + 1, stored in task j0's turn
+        pr_nn = p.tpair[s.j0 + 2u < s.j1 ? s.j0 + 2u : last];           // the pair of task j0 + 2: its row is requested in task j0's turn
+    }
     wv::barrier();
     for (u32 t = s.j0; t < s.j1; ++t) {
         const RTask r = a.rt[t];   // (its cache line was touched two tasks ago, for the three words)
         const u32 set = (t - s.j0) & 1u, tree = tree_n, tbase = l_off[tree], ntn = l_off[tree + 1] - tbase;
         u32 hiq[SCAN_NQ], enq[SCAN_NQ];   // (the owner of the pick needs its key half and list entry again)
         WV_UNROLL
-        for (int q = 0; q < SCAN_NQ; ++q) { hiq[q] = hin[q]; enq[q] = ein[q]; }
+        for (int q = 0; q < SCAN_NQ; ++q) { hiq[q] = hin[q]; if (!SCAN_CM) enq[q] = ein[q]; }
         u64* leafmin = lmin + (size_t)set * M;
         u32* tsum = lsum + (size_t)set * M;
         u32* noroom = lnor + (size_t)set * M;
         const u32 gset = a.n_rg ? a.tg[t] : 0u;
+        u32 fix_c = LIST_EMPTY, fix_e = LIST_EMPTY;   // SCAN_CM: the row this thread placed a task of the NEXT task's service on, and its list entry
         // the next task's set (last read by the walk two tasks ago, in front of that task's second barrier)
-        for (u32 i = tid; i < M; i += SCAN_THREADS) { lmin[(size_t)(set ^ 1u) * M + i] = KEY_NONE; lsum[(size_t)(set ^ 1u) * M + i] = 0; lnor[(size_t)(set ^ 1u) * M + i] = 0; }
+        if (!SCAN_CM)
+            for (u32 i = tid; i < M; i += SCAN_THREADS) { lmin[(size_t)(set ^ 1u) * M + i] = KEY_NONE; lsum[(size_t)(set ^ 1u) * M + i] = 0; lnor[(size_t)(set ^ 1u) * M + i] = 0; }
+        else {
+            const u32* bx = p.base + (size_t)p.tpair[t + 1u < s.j1 ? t + 1u : last] * M;   // (read beyond SCAN_THREADS branches only)
+            for (u32 i = tid; i < M; i += SCAN_THREADS) { lmin[(size_t)(set ^ 1u) * M + i] = KEY_NONE; lsum[(size_t)(set ^ 1u) * M + i] = i == tid ? bn : bx[i]; lnor[(size_t)(set ^ 1u) * M + i] = 0; }
+            bn = tid < M ? p.base[(size_t)pr_nn * M + tid] : 0u;   // the row of task t + 2
+            pr_nn = p.tpair[t + 3u < s.j1 ? t + 3u : last];
+        }
         // ---- every thread: its nodes into their leaves
         WV_UNROLL
         for (int q = 0; q < SCAN_NQ; ++q) {
-            const u32 n = tid + (u32)q * SCAN_THREADS;
+            const u32 n = tid + (u32)q * SCAN_THREADS, m = SCAN_CM ? real[q] : n;   // n: the row (SCAN_CM: the compact index), m: the node
             if (!((present >> q) & 1u)) continue;
-            const u32 w = n >> 6;
-            const u64 bit = 1ull << (n & 63);
+            const u32 w = m >> 6;
+            const u64 bit = 1ull << (m & 63);
             const u32 hi = hiq[q], lf = lfn[q];
             if (lf >= ntn) continue;   // (tables of another nodeSet: the launcher builds them from the one the batch was prepared for)
             if (hi & 0xFFFFFFu) wv::lds_add32(tsum + lf, hi & 0xFFFFFFu);   // tree.tasks: every node of the nodeSet, feasible or not
-            if (!(scn[q] & bit)) continue;   // (the static class row holds valid & ready & constraints & platform & plugins)
+            if (SCAN_CM ? !((scn[q] >> (m & 31u)) & 1u) : !(scn[q] & bit)) continue;   // (the static class row holds valid & ready & constraints & platform & plugins)
             if ((r.flags & RT_RES) && !(r.cpu <= cpu[n] && r.mem <= mem[n])) continue;
             bool ok = true;
             if (gset)
                 for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) {
                     const u32 row = a.gs_row[g];
-                    if (a.gcnt[(size_t)a.rg_kind[row] * a.gstride + n] < a.rg_val[row]) ok = false;   // HasEnough, validate.go:24-52
+                    if (a.gcnt[(size_t)a.rg_kind[row] * a.gstride + m] < a.rg_val[row]) ok = false;   // HasEnough, validate.go:24-52
                 }
             if (ok && (r.flags & RT_PORTS))
                 for (u32 z = a.pset_off[r.pset]; z < a.pset_off[r.pset + 1]; ++z)
@@ -268,12 +346,19 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
             ++ni;
         } else {
             if ((gn & (SCAN_THREADS - 1u)) == tid) {
-                const u32 nd = gn, w = nd >> 6;
-                const u64 bit = 1ull << (nd & 63);
+                const u32 nd = gn;
+                u32 m = nd;   // the node behind the row
+                if (SCAN_CM) {
+                    WV_UNROLL
+                    for (int q = 0; q < SCAN_NQ; ++q)
+                        if (tid + (u32)q * SCAN_THREADS == nd) m = real[q];
+                }
+                const u32 w = m >> 6;
+                const u64 bit = 1ull << (m & 63);
                 if (r.cpu) cpu[nd] -= r.cpu;
                 if (r.mem) mem[nd] -= r.mem;
                 if (gset)
-                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) a.gcnt[(size_t)a.rg_kind[a.gs_row[g]] * a.gstride + nd] -= a.rg_val[a.gs_row[g]];   // Claim
+                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) a.gcnt[(size_t)a.rg_kind[a.gs_row[g]] * a.gstride + m] -= a.rg_val[a.gs_row[g]];   // Claim
                 if (r.flags & RT_PORTS)
                     for (u32 q = a.pset_off[r.pset]; q < a.pset_off[r.pset + 1]; ++q) wv::g_or64(a.portmap + (size_t)a.pset_ids[q] * Wn + w, bit);
                 if (!(r.flags & RT_UNCOUNTED)) {
@@ -281,13 +366,14 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
                     u32 hi = 0, entry = LIST_EMPTY;
                     WV_UNROLL
                     for (int q = 0; q < SCAN_NQ; ++q)
-                        if (tid + (u32)q * SCAN_THREADS == nd) { hi = hiq[q]; entry = enq[q]; }
+                        if (tid + (u32)q * SCAN_THREADS == nd) { hi = hiq[q]; entry = SCAN_CM ? ein[q] : enq[q]; }
+                    if (SCAN_CM) hi = (u32)(gk >> 32);   // (the pick's key carries its key half: hiq is not kept past the evaluation)
                     hi += 1u;
                     if ((hi & 0xFFFFFFu) == 0) a.blk->error = ERR_GROUP_RANGE;
                     s.hmat[(size_t)r.svc * N + nd] = hi;
                     if (entry == LIST_EMPTY) {
                         wv::g_or64(a.X + (size_t)r.svc * a.xs + w, bit);
-                        a.list_node[r.slot] = nd;
+                        a.list_node[r.slot] = m;
                         a.list_svc[r.slot] = 1;
                         a.list_fail[r.slot] = 0;
                         s.emat[(size_t)r.svc * N + nd] = r.slot;
@@ -297,21 +383,36 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
                     if (svc_n == r.svc) {   // the next task is of the same service: what it read of this node is a placement old
                         WV_UNROLL
                         for (int q = 0; q < SCAN_NQ; ++q)
-                            if (tid + (u32)q * SCAN_THREADS == nd) { hin[q] = hi; ein[q] = entry; }
+                            if (tid + (u32)q * SCAN_THREADS == nd) { hin[q] = hi; if (!SCAN_CM) ein[q] = entry; }
+                        if (SCAN_CM) { fix_c = nd; fix_e = entry; }
                     }
                 }
                 const int32_t prev = lastc[nd];
-                a.log_node[nc] = nd;
+                a.log_node[nc] = m;
                 a.log_task[nc] = t;
                 a.log_prev[nc] = prev;
                 lastc[nd] = (int32_t)nc;
-                a.out_node[t] = (int32_t)nd;
+                a.out_node[t] = (int32_t)m;
             }
             ++nc;
         }
+        if (SCAN_CM && t + 1 < s.j1) {   // the next task's list entries (the cell this thread has just written: from the register)
+            ahead_entries(svc_n);
+            WV_UNROLL
+            for (int q = 0; q < SCAN_NQ; ++q)
+                if (tid + (u32)q * SCAN_THREADS == fix_c) ein[q] = fix_e;
+        }
         // (no third barrier: a node's row and its matrix cells are read and written by its owner only; the per-tree words alternate)
     }
-    for (u32 n = tid; n < N; n += SCAN_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    if (!SCAN_CM)
+        for (u32 n = tid; n < N; n += SCAN_THREADS) { a.cpu[n] = cpu[n]; a.mem[n] = mem[n]; a.total[n] = tot[n]; a.last[n] = lastc[n]; }
+    else {   // the union's nodes only: no other node was read, none is written
+        WV_UNROLL
+        for (int q = 0; q < SCAN_NQ; ++q) {
+            const u32 n = tid + (u32)q * SCAN_THREADS, m = real[q];
+            if (n < N) { a.cpu[m] = cpu[n]; a.mem[m] = mem[n]; a.total[m] = tot[n]; a.last[m] = lastc[n]; }
+        }
+    }
     if (tid == 0) {
         a.ctl->ncommit = nc;
         a.ctl->ninf = ni;

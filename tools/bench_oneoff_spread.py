@@ -14,7 +14,15 @@ profiles/oneoff_spread.json).
                   more tasks than nodes), where the engine hands them to the scan resolver (k_scan / k_scanb): the counters say
                   which resolver took how many.
 
-usage: python tools/bench_oneoff_spread.py [--tasks 20000] [--services 200] [--nodes 1000] [--zones 5] [--runs 3] [--out FILE]"""
+  --pool        the COMPACT form instead of (a) - (c) (csrc/swp_scan_spread.hpp, k_scan_spread<.., true>: a nodeSet beyond 4 096 slots):
+                  --pool-nodes nodes (default 10 000) of which every --pool-every-th (10) carries pool=a, spread over --zones zones;
+                  the tasks are constrained to the pool. The tick with the knob off (the parent's behaviour: the batch is refused
+                  there, the host layer splits) and on, --runs fresh schedulers each; then the PLAIN instance on a cluster made of
+                  just the pool's nodes, knob on: the difference is the cost of compaction (probe, gather, base sums, indirection).
+                  e.g. --pool --out profiles/oneoff_spread_compact.json
+
+usage: python tools/bench_oneoff_spread.py [--tasks 20000] [--services 200] [--nodes 1000] [--zones 5] [--runs 3] [--out FILE]
+       python tools/bench_oneoff_spread.py --pool [--pool-nodes 10000] [--pool-every 10] [--tasks 20000] [--services 200] [--runs 3] [--out FILE]"""
 import argparse
 import json
 import os
@@ -70,6 +78,69 @@ def one_tick(a, knob, profile=False):
     return ms, {x["ID"]: x["NodeID"] for x in d}, st
 
 
+def pool_node_doc(i, zones, every):
+    labels = {"zone": "z%d" % (i // every % zones)}
+    if i % every == 0:
+        labels["pool"] = "a"
+    return {"ID": "n%05d" % i, "Status": {"State": READY}, "Spec": {"Annotations": {"Labels": labels}},
+            "Description": {"Resources": {"NanoCPUs": 64 * 10**9, "MemoryBytes": 256 << 30}}}
+
+
+def pool_tick(a, knob, only_pool, profile=False):
+    """one tick of --tasks pooled spread tasks; only_pool: the cluster is just the pool's nodes (the plain instance)"""
+    if knob:
+        os.environ[KNOB] = "1"
+    else:
+        os.environ.pop(KNOB, None)
+    s = swhost.HostScheduler(profile=profile)
+    for i in range(a.pool_nodes):
+        if not only_pool or i % a.pool_every == 0:
+            s.create_node(pool_node_doc(i, a.zones, a.pool_every))
+    for k in range(a.services):
+        s.set_service("svc%03d" % k)
+    for j in range(a.tasks):
+        t = task_doc(j, a.services)
+        t["Spec"]["Placement"]["Constraints"] = ["node.labels.pool==a"]
+        s.create_task(t)
+    t0 = time.perf_counter()
+    d = s.tick()
+    ms = (time.perf_counter() - t0) * 1e3
+    return ms, {x["ID"]: x["NodeID"] for x in d}, s.e.stats()
+
+
+def pool_main(a):
+    os.environ["SWP_HOST"] = "cxx"
+    one_tick(argparse.Namespace(nodes=64, zones=a.zones, services=4, tasks=64), True)   # warm: modules, pools
+    off, on, plain, want = [], [], [], None
+    for r in range(a.runs):
+        for knob in ((False, True) if r % 2 == 0 else (True, False)):
+            ms, dec, st = pool_tick(a, knob, False)
+            (on if knob else off).append(ms)
+            if want is None:
+                want = dec
+            assert dec == want, "the two paths decide the tick differently"
+            if knob:
+                assert st["scan_tasks"] == a.tasks and st["scan_launches"] == 1, st
+        ms, dec, st = pool_tick(a, True, True)
+        assert dec == want and st["scan_tasks"] == a.tasks, "the pool alone decides the tick differently"
+        plain.append(ms)
+    eng = {}
+    for name, only_pool in (("compact", False), ("plain_pool_alone", True)):
+        ms, _, st = pool_tick(a, True, only_pool, profile=True)
+        eng[name] = {"tick_ms_with_profile": round(ms, 3), "segment_ms": round(st["ms_scan"], 3), "batch_ms_total": round(st["ms_total"], 3),
+                     "segment_us_per_task": round(st["ms_scan"] * 1e3 / a.tasks, 3)}
+    out = {"tool": "bench_oneoff_spread --pool", "tasks": a.tasks, "services": a.services, "nodes": a.pool_nodes, "pool_nodes": len(range(0, a.pool_nodes, a.pool_every)),
+           "zones": a.zones, "runs": a.runs, "placed": sum(1 for v in want.values() if v),
+           "tick_ms": {"knob_off_parent_path": summary(off), "knob_on_compact": summary(on), "knob_on_plain_pool_alone": summary(plain),
+                       "off_over_on_median": round(statistics.median(off) / statistics.median(on), 2),
+                       "compact_over_plain_median": round(statistics.median(on) / statistics.median(plain), 3)},
+           "engine_knob_on": eng}
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
 def summary(v):
     return {"runs": [round(x, 3) for x in v], "min": round(min(v), 3), "median": round(statistics.median(v), 3), "max": round(max(v), 3), "spread": round(max(v) - min(v), 3)}
 
@@ -100,7 +171,12 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--scan-shape", default="10,500,20000", help="services,nodes,tasks of (c)'s second shape")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pool", action="store_true", help="the compact form: a labelled pool of a cluster beyond 4 096 nodes")
+    ap.add_argument("--pool-nodes", type=int, default=10_000)
+    ap.add_argument("--pool-every", type=int, default=10)
     a = ap.parse_args()
+    if a.pool:
+        return pool_main(a)
     os.environ["SWP_HOST"] = "cxx"
     one_tick(argparse.Namespace(nodes=64, zones=a.zones, services=4, tasks=64), True)   # warm: modules, pools
     off, on, want = [], [], None
