@@ -320,8 +320,13 @@ typedef struct {
  *     that is every segment; on a larger one it is the UNION of the static class rows its tasks name — the nodes that are READY and
  *     pass the Constraint, Platform and Plugin filters of one of them: services constrained to a labelled pool of a large cluster
  *     (the compact instance; the nodes outside the union still weigh on the tree with their tasks of the service). The class rows
- *     exist on the device only: the preparation computes them and probes every segment. A segment with one unconstrained task has
- *     the whole nodeSet as its union;
+ *     exist on the device only: the preparation computes them and probes every segment. A segment whose union is wider — one
+ *     unconstrained plain task riding along makes it the whole nodeSet; two pools that fit one by one — is not refused: the
+ *     preparation CUTS it (k_spread_cut) in front of the first task whose class row takes the union of the piece so far past the
+ *     limit; a task without preferences found there goes, with the plain tasks behind it, to the block / scan resolver, and the
+ *     next piece starts at the next task with preferences. Cutting is exact: the pieces decide the tasks in array order. What stays
+ *     refused is a task with preferences whose OWN class row has more than 4 096 nodes (and a segment of more than 4 096 pieces):
+ *     with the message of the segment as a whole;
  *   - the node rows (24 bytes a slot, or a node of the largest union) and the trees of the batch's spread sets — 32 bytes per branch
  *     of the largest tree, 20 per branch of all of them, 32 per level — fit 160 KiB - 512 bytes of LDS (4 096 nodes leave room for
  *     some 1 200 branches);
@@ -330,7 +335,8 @@ typedef struct {
  * (swp_shard_*), the refusal is SWP_EUNSUPPORTED as before — the message names the limit — with engine and mirror untouched: such a task
  * goes through swp_schedule_groups as a group of one. swp_fit_pairs* refuse templates with preferences as before.
  * On a nodeSet beyond 4 096 slots swp_batch_run checks the unions again before its first placing launch — a node upserted since the
- * preparation is sent to the device first — and refuses in the same way, rows and mirror untouched.
+ * preparation is sent to the device first — and refuses in the same way, rows and mirror untouched. It does not cut again: a label
+ * that moved since the preparation and widens a piece past the limit is a refusal, and a fresh preparation cuts anew.
  * (swp_stats: a spread segment counts as a stretch of the scan resolver — scan_launches, scan_tasks, ms_scan.) */
 int swp_schedule_batch(swp_engine*, const swp_task_desc* tasks, uint32_t n_tasks,
                        int32_t* out_node, uint32_t* out_fail_hist /* [n_tasks][SWP_NFILTERS] */);

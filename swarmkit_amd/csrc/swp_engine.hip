@@ -482,6 +482,7 @@ struct swp_batch {
     bool sp_compact = false;
     std::vector<uint32_t> sp_pair, sp_pair_svc, sp_pair_tree, sp_nc;
     DevBuf d_sp_pair, d_sp_psvc, d_sp_ptree, d_sp_base, d_sp_cnc;
+    DevBuf d_sp_cut;                       // the piece lists of the segments cut at the preparation (k_spread_cut)
     bool wide_keys = false;                // an exception entry beyond the 8 + 24 bit keys of k_waterfill and the scan resolver: the block resolver decides alone
     DevBuf d_wf;                           // k_waterfill scratch: [3][n_nodes] u32
     // the streamed run (swp_batch_run_streamed, swp_publish.hpp): the host-visible block k_publish writes — the mark counter on a line
@@ -2208,7 +2209,27 @@ int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra
 // (b->sp_trees, built by the caller; the base sums take none: a register a thread, swp_scan_spread.hpp). Refuses with nothing written
 // but the batch's own probe buffers. The unions themselves are built again, segment by segment, when the segments run (the scan
 // stretches in between share the buffers).
-int spread_probe(swp_engine* e, swp_batch* b) {
+// the limit over the counts in b->sp_nc. wide: instead of refusing, the positions in b->segs of the segments beyond it
+int spread_limit(swp_engine* e, swp_batch* b, std::vector<uint32_t>* wide) {
+    const SpreadTrees& t = b->sp_trees;
+    uint32_t k = 0;
+    for (size_t i = 0; i < b->segs.size(); ++i) {
+        const swp_batch::Seg& sg = b->segs[i];
+        if (!sg.spread) continue;
+        const uint32_t nc = b->sp_nc[k++];
+        const bool fits = scan_spread_lds_size(nc, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) <= R6_LDS_BUDGET;
+        if (wide && (nc > scan_max_nodes() || !fits)) { wide->push_back((uint32_t)i); continue; }
+        if (nc > scan_max_nodes())
+            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (a batch takes them where the nodes its segment's tasks can use number at most %u: the union of the class rows of segment %u, tasks [%u, %u), has %u of this nodeSet's %u)",
+                           scan_max_nodes(), k - 1, sg.j0, sg.j0 + sg.n, nc, e->n_nodes);
+        if (!fits)
+            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (the %u nodes of the union of segment %u, tasks [%u, %u), and trees of %u branches, the largest of %u over %u levels, exceed the spread kernel's LDS; at most %u nodes in any case)",
+                           nc, k - 1, sg.j0, sg.j0 + sg.n, t.tree_off.back(), t.max_ntn, t.max_depth, scan_max_nodes());
+    }
+    return SWP_OK;
+}
+
+int spread_probe(swp_engine* e, swp_batch* b, std::vector<uint32_t>* wide = nullptr) {
     uint32_t n_seg = 0;
     for (const swp_batch::Seg& sg : b->segs) n_seg += sg.spread ? 1u : 0u;
     b->sp_nc.assign(n_seg, 0);
@@ -2233,26 +2254,109 @@ int spread_probe(swp_engine* e, swp_batch* b) {
     }
     HIPCHECK(e, hipMemcpyAsync(b->sp_nc.data(), b->d_sp_cnc.p, (size_t)n_seg * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHECK(e, hipStreamSynchronize(e->stream));
+    return spread_limit(e, b, wide);
+}
+
+// Segments the first probe found too wide (`wide`: their positions in b->segs) are CUT where the union of the class rows passes the
+// limit (k_spread_cut, swp_scan_spread.hpp: the rule) — an unconstrained plain task that rides along, two pools that fit one by one —
+// instead of refusing the batch: a launch per such segment, the piece lists back in one copy, b->segs rewritten, every new segment
+// probed. A segment that cannot be cut (a task with preferences whose own row is too wide, more than SPREAD_CUT_PIECES pieces) is
+// refused as the first probe would have refused it: the same words, for the segment as spread_segments made it.
+constexpr uint32_t SPREAD_CUT_PIECES = 4096;
+int spread_cut(swp_engine* e, swp_batch* b, const std::vector<uint32_t>& wide, double first_probe_ms) {
+    const std::vector<swp_batch::Seg> segs0 = b->segs;
+    const std::vector<uint32_t> nc0 = b->sp_nc;
+    auto refuse = [&]() {
+        b->segs = segs0;
+        b->sp_nc = nc0;
+        return spread_limit(e, b, nullptr);
+    };
+    const bool dbg = getenv("SWP_DEBUG_PREPARE") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    // L: the most nodes the spread kernel takes next to this batch's trees
     const SpreadTrees& t = b->sp_trees;
-    k = 0;
-    for (const swp_batch::Seg& sg : b->segs) {
-        if (!sg.spread) continue;
-        const uint32_t nc = b->sp_nc[k++];
-        if (nc > scan_max_nodes())
-            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (a batch takes them where the nodes its segment's tasks can use number at most %u: the union of the class rows of segment %u, tasks [%u, %u), has %u of this nodeSet's %u)",
-                           scan_max_nodes(), k - 1, sg.j0, sg.j0 + sg.n, nc, e->n_nodes);
-        if (scan_spread_lds_size(nc, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) > R6_LDS_BUDGET)
-            return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (the %u nodes of the union of segment %u, tasks [%u, %u), and trees of %u branches, the largest of %u over %u levels, exceed the spread kernel's LDS; at most %u nodes in any case)",
-                           nc, k - 1, sg.j0, sg.j0 + sg.n, t.tree_off.back(), t.max_ntn, t.max_depth, scan_max_nodes());
+    auto fits = [&](uint32_t nc) { return scan_spread_lds_size(nc, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) <= R6_LDS_BUDGET; };
+    if (!fits(0)) return refuse();
+    uint32_t L = 0;
+    for (uint32_t hi = scan_max_nodes(); L < hi;) {   // (the size grows with the node count)
+        const uint32_t mid = L + (hi - L + 1u) / 2u;
+        if (fits(mid)) L = mid;
+        else hi = mid - 1u;
+    }
+    const uint32_t Wn = n_words_of(e->n_nodes);
+    if (spread_cut_lds(b->n_sc, Wn, false) > R6_LDS_BUDGET) return refuse();
+    ScanArgs sa{};
+    if (int rc = scan_compact_bufs(e, b, &sa)) return rc;   // (cu: the piece's union where LDS does not hold it)
+    if (int rc = upload(e, b->d_sp_tree, b->sp_tree)) return rc;   // != 0: the task has preferences (tree 0 is the tree of no levels)
+    std::vector<size_t> off;
+    size_t words = 0;
+    for (uint32_t i : wide) {
+        off.push_back(words);
+        words += CUT_HEAD + (size_t)3 * std::min(segs0[i].n, SPREAD_CUT_PIECES);
+    }
+    HIPCHECK(e, b->d_sp_cut.reserve(words * 4));
+    for (size_t q = 0; q < wide.size(); ++q) {
+        const swp_batch::Seg& sg = segs0[wide[q]];
+        CutArgs ca{};
+        ca.rt = b->d_rt.as<RTask>();
+        ca.pref = b->d_sp_tree.as<uint32_t>();
+        ca.sc = b->d_sc.as<u64>();
+        ca.cu = sa.cu;
+        ca.out = b->d_sp_cut.as<uint32_t>() + off[q];
+        ca.j0 = sg.j0;
+        ca.j1 = sg.j0 + sg.n;
+        ca.n_sc = b->n_sc;
+        ca.n_words = Wn;
+        ca.L = L;
+        ca.max_pieces = std::min(sg.n, SPREAD_CUT_PIECES);
+        const hipError_t r = launch_spread_cut(ca, e->stream, e->device);
+        if (r != hipSuccess) return e->fail(SWP_EHIP, "k_spread_cut launch: %s", hipGetErrorString(r));
+    }
+    std::vector<uint32_t> lists(words);
+    HIPCHECK(e, hipMemcpyAsync(lists.data(), b->d_sp_cut.p, words * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<swp_batch::Seg> cut;
+    auto push = [&](const swp_batch::Seg& sg) {   // adjacent plain stretches are one stretch, as build_batch leaves them
+        if (!cut.empty() && !sg.run && !sg.spread && !cut.back().run && !cut.back().spread) cut.back().n += sg.n;
+        else cut.push_back(sg);
+    };
+    size_t q = 0;
+    for (size_t i = 0; i < segs0.size(); ++i) {
+        if (q == wide.size() || wide[q] != i) { push(segs0[i]); continue; }
+        const uint32_t* o = lists.data() + off[q++];
+        if (o[0] != CUT_OK) return refuse();
+        uint32_t at = segs0[i].j0;
+        for (uint32_t k = 0; k < o[2]; ++k) {
+            const uint32_t* pc = o + CUT_HEAD + 3 * k;
+            if (pc[0] != at || pc[1] == 0 || pc[1] > segs0[i].j0 + segs0[i].n - at) return e->fail(SWP_EHIP, "k_spread_cut: piece %u of segment [%u, %u) is [%u, +%u)", k, segs0[i].j0, segs0[i].j0 + segs0[i].n, pc[0], pc[1]);
+            push(swp_batch::Seg{pc[0], pc[1], false, pc[2] != 0});
+            at += pc[1];
+        }
+        if (at != segs0[i].j0 + segs0[i].n) return e->fail(SWP_EHIP, "k_spread_cut: the pieces of segment [%u, %u) end at task %u", segs0[i].j0, segs0[i].j0 + segs0[i].n, at);
+    }
+    b->segs = std::move(cut);
+    std::vector<uint32_t> still;
+    if (int rc = spread_probe(e, b, &still)) return rc;
+    if (!still.empty()) return refuse();   // (the kernel's counts and the probe's are of the same rows: not expected)
+    if (dbg) {
+        const auto t2 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[swp] spread cut: %zu of %zu segments too wide, limit %u nodes: %zu segments now; first probe %.3f ms, cut %.3f ms, second probe %.3f ms\n", wide.size(), segs0.size(), L, b->segs.size(),
+                first_probe_ms, std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(t2 - t1).count());
     }
     return SWP_OK;
 }
 
-// ... at swp_batch_prepare, behind the node flush and the batch's upload: the class rows exist only on the device
+// ... at swp_batch_prepare, behind the node flush and the batch's upload: the class rows exist only on the device. Segments that are
+// too wide are cut here (spread_cut) — and only here: the run probes the segments as they were prepared (spread_tables).
 int spread_prepare_probe(swp_engine* e, swp_batch* b) {
     if (!b->T || !e->n_nodes) return SWP_OK;
     if (int rc = run_classes(e, b)) return rc;
-    return spread_probe(e, b);
+    std::vector<uint32_t> wide;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = spread_probe(e, b, &wide)) return rc;
+    if (wide.empty()) return SWP_OK;
+    return spread_cut(e, b, wide, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 // A batch with spread segments, once per run and before its first launch: the trees of its spread sets from the nodeSet as the mirror

@@ -70,6 +70,9 @@ hipError_t launch_scan_spread(const SpreadArgs& p, hipStream_t st, int dev);    
 hipError_t launch_scan_matrices_compact(const ScanArgs& s, hipStream_t st);     // k_scan_fill_c + k_scan_lists_c alone: the matrices over the union's s.n_c columns (behind launch_scan_probe)
 // the compact spread instance, behind launch_scan_probe + launch_scan_matrices_compact: k_spread_base (the pairs' leaf sums over the nodes outside the union) + k_scan_spread<.., true>
 hipError_t launch_scan_spread_compact(const SpreadArgs& p, const uint32_t* pair_svc, const uint32_t* pair_tree, uint32_t* base, hipStream_t st, int dev);
+// a compact spread segment whose union is too wide: the pieces to cut it into (k_spread_cut, swp_scan_spread.hpp), one workgroup
+struct CutArgs;
+hipError_t launch_spread_cut(CutArgs p, hipStream_t st, int dev);
 
 // task groups (swp_groups.hip)
 struct Groups2Args;

@@ -53,4 +53,17 @@ hipError_t launch_scan_spread_compact(const SpreadArgs& p, const uint32_t* pair_
     }
 }
 
+// ---- a compact segment too wide for the kernel: where to cut it (k_spread_cut), one workgroup
+// the piece's union in LDS where it fits next to the flags, else in p.cu; hipErrorInvalidValue: not even the flags fit (the caller refuses)
+hipError_t launch_spread_cut(CutArgs p, hipStream_t st, int dev) {
+    if (p.j0 >= p.j1 || p.max_pieces == 0 || p.n_sc == 0) return hipErrorInvalidValue;
+    p.u_lds = spread_cut_lds(p.n_sc, p.n_words, true) <= (size_t)160 * 1024 - 512 ? 1u : 0u;
+    const size_t lds = spread_cut_lds(p.n_sc, p.n_words, p.u_lds != 0);
+    if (lds > (size_t)160 * 1024 - 512 || (!p.u_lds && !p.cu)) return hipErrorInvalidValue;
+    hipError_t r;
+    if (lds > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(&k_spread_cut), dev)) != hipSuccess) return r;
+    hipLaunchKernelGGL(k_spread_cut, dim3(1), dim3(SCAN_THREADS), lds, st, p);
+    return hipGetLastError();
+}
+
 }  // namespace swpdev

@@ -57,7 +57,122 @@ inline __host__ __device__ size_t scan_lds_sp(u32 n_nodes, u32 max_ntn, u32 max_
     return (((size_t)n_nodes * 24 + 15) & ~(size_t)15) + 16 + (size_t)2 * max_ntn * 16 + (size_t)(max_depth + 1) * sizeof(SpFrame) + ((size_t)n_trees + 1 + (size_t)5 * tot_ntn) * 4;
 }
 
+// ---- a compact spread segment whose union is too wide for the kernel above: k_spread_cut finds where to CUT it
+// The rule, over the static class rows row(t) = sc[rt[t].sc] of the segment's tasks [j0, j1) and a limit of L nodes:
+//   a piece starts at a task with preferences (j0 is one) and takes the tasks behind it while the union of their rows stays at or
+//   below L nodes; in front of the first task k that does not fit the piece ends. If k has preferences the next piece starts at it;
+//   else the tasks from k up to the next task with preferences (or j1) form a PLAIN piece — the block / scan resolver's — and the next
+//   piece starts behind it. A piece's first task whose own row exceeds L cannot be taken at all: CUT_OWN_ROW.
+// Cutting is exact wherever it happens (swp_rounds.hpp spread_segments): consecutive pieces decide the tasks in array order.
+#define CUT_OK 0u
+#define CUT_OWN_ROW 1u      // out[1]: the task
+#define CUT_FULL 2u         // more than max_pieces pieces
+#define CUT_HEAD 4u         // words in front of the piece list
+struct CutArgs {
+    const RTask* rt;        // the batch's tasks (rt[].sc: the static class row)
+    const u32* pref;        // [tasks of the batch] != 0: the task has preferences
+    const u64* sc;          // [n_sc][n_words] the static class rows
+    u64* cu;                // [n_words] the piece's union when it does not fit in LDS (u_lds == 0)
+    u32* out;               // [CUT_HEAD + 3 * max_pieces]: status, task, pieces, counts made; then (first, count, spread) per piece
+    u32 j0, j1, n_sc, n_words, L, max_pieces, u_lds;
+};
+// a mask and a sum per wave, a chunk's class rows and preference words, a flag per class row, the union's words
+inline __host__ __device__ size_t spread_cut_lds(u32 n_sc, u32 n_words, bool u_lds) {
+    return (size_t)(SCAN_THREADS / 64) * 12 + (size_t)2 * SCAN_THREADS * 4 + (((size_t)n_sc * 4 + 7) & ~(size_t)7) + (u_lds ? (size_t)n_words * 8 : 0);
+}
+
 #ifdef SWP_SCAN_SPREAD_KERNEL
+// ONE workgroup. The tasks are taken SCAN_THREADS at a time, a task a thread: its class row and preference word go to LDS once, and
+// a flag per class row says whether the piece holds the row already. A ballot of the tasks whose row it does not hold yet finds the
+// next task that costs anything; the tasks in front of it join the piece unseen. That task costs ONE count: every thread takes the
+// words w = tid, tid + SCAN_THREADS, ... of popc(U | row), a DPP reduction per wave, a word per wave in LDS. A thread reads and writes
+// only ITS words of U (in LDS or, beyond it, in cu), so U needs no barrier of its own. Every branch below is uniform over the
+// workgroup: what it tests was read from LDS behind a barrier.
+//   barrier A: the waves' masks are written;  barrier B: the waves' sums are written (and the masks read);  barrier C: a chunk's words
+//   are written (and everything of the chunk in front read). A flag is written in front of A or B and read behind C.
+WV_KERNEL(SCAN_THREADS) void k_spread_cut(CutArgs p) {
+    constexpr u32 NW = SCAN_THREADS / 64;
+    const u32 tid = wv::tid(), lane = wv::lane(), wave = tid >> 6, Wn = p.n_words;
+    u64* wmask = wv::lds();                                  // [NW] a wave's tasks that still cost a count (or: that have preferences)
+    u32* wsum = reinterpret_cast<u32*>(wmask + NW);          // [NW] a wave's share of a count
+    u32* tsc = wsum + NW;                                    // [SCAN_THREADS] the chunk's class rows
+    u32* tpf = tsc + SCAN_THREADS;                           // [SCAN_THREADS] ... and preference words
+    u32* flag = tpf + SCAN_THREADS;                          // [n_sc] the piece holds the row
+    u64* U = p.u_lds ? reinterpret_cast<u64*>(flag + ((p.n_sc + 1u) & ~1u)) : p.cu;
+    for (u32 w = tid; w < Wn; w += SCAN_THREADS) U[w] = 0;
+    for (u32 c = tid; c < p.n_sc; c += SCAN_THREADS) flag[c] = 0;
+    u32 j = p.j0, np = 0, counts = 0, status = CUT_OK, bad = 0, skip0 = 0;
+    bool fresh = true, skipping = false;   // fresh: the piece holds no row yet; skipping: inside a plain piece, looking for its end
+    auto emit = [&](u32 first, u32 n, u32 spread) {
+        if (np == p.max_pieces) { status = CUT_FULL; return; }
+        if (tid == 0) { p.out[CUT_HEAD + 3 * np] = first; p.out[CUT_HEAD + 3 * np + 1] = n; p.out[CUT_HEAD + 3 * np + 2] = spread; }
+        ++np;
+    };
+    for (u32 c0 = p.j0; c0 < p.j1 && status == CUT_OK; c0 += SCAN_THREADS) {
+        const u32 cend = p.j1 - c0 < SCAN_THREADS ? p.j1 - c0 : SCAN_THREADS;
+        const bool have = tid < cend;
+        const u32 my_sc = have ? p.rt[c0 + tid].sc : 0u, my_pf = have ? p.pref[c0 + tid] : 0u;
+        tsc[tid] = my_sc;
+        tpf[tid] = my_pf;
+        wv::barrier();   // C
+        bool need = have && !flag[my_sc];
+        u32 cur = 0;   // the chunk's tasks in front of it are decided
+        while (cur < cend && status == CUT_OK) {
+            const u64 m = wv::ballot(tid >= cur && (skipping ? have && my_pf != 0 : need));
+            if (lane == 0) wmask[wave] = m;
+            wv::barrier();   // A
+            u32 i = cend;
+            for (u32 v = 0; v < NW; ++v) {
+                const u64 x = wmask[v];
+                if (x) { i = v * 64u + (u32)wv::ffs64(x); break; }
+            }
+            if (i == cend) break;   // the rest of the chunk rides along (the next write of wmask lies behind C)
+            if (skipping) {   // the plain piece ends in front of this task with preferences: the next piece starts at it
+                emit(skip0, c0 + i - skip0, 0u);
+                skipping = false;
+                j = c0 + i;
+                cur = i;
+                wv::barrier();   // (the masks are read: no B on this path)
+                continue;
+            }
+            const u32 r = tsc[i];
+            const u64* row = p.sc + (size_t)r * Wn;
+            u32 part = 0;
+            for (u32 w = tid; w < Wn; w += SCAN_THREADS) part += (u32)wv::popc64(U[w] | row[w]);
+            const u32 incl = wv::scan_incl_u32(part);
+            if (lane == 63) wsum[wave] = incl;
+            wv::barrier();   // B
+            u32 total = 0;
+            for (u32 v = 0; v < NW; ++v) total += wsum[v];
+            ++counts;
+            if (total <= p.L) {   // the task joins the piece, and with it every task of the same row
+                for (u32 w = tid; w < Wn; w += SCAN_THREADS) U[w] |= row[w];
+                if (tid == 0) flag[r] = 1u;
+                if (my_sc == r) need = false;
+                fresh = false;
+                cur = i + 1u;
+            } else if (fresh) {   // its own row is too wide
+                status = CUT_OWN_ROW;
+                bad = c0 + i;
+            } else {   // the cut: the piece ends in front of the task, which is looked at again with nothing in U
+                emit(j, c0 + i - j, 1u);
+                for (u32 w = tid; w < Wn; w += SCAN_THREADS) U[w] = 0;
+                for (u32 c = tid; c < p.n_sc; c += SCAN_THREADS) flag[c] = 0;
+                fresh = true;
+                need = have;
+                cur = i;
+                if (tpf[i]) j = c0 + i;
+                else { skipping = true; skip0 = c0 + i; }
+            }
+        }
+    }
+    if (status == CUT_OK) {
+        if (skipping) emit(skip0, p.j1 - skip0, 0u);
+        else emit(j, p.j1 - j, 1u);
+    }
+    if (tid == 0) { p.out[0] = status; p.out[1] = bad; p.out[2] = np; p.out[3] = counts; }
+}
+
 // The compact instance's base sums. nodeSet.tree adds a node's count of the service to every branch on its path whether the node passes
 // the filters or not, so a node outside the segment's union — never picked, never changed inside the segment — still weighs on the
 // walk: with a constant, per (service, tree) pair. base[pair][leaf] = the sum of list_svc over the service's list entries whose node lies

@@ -20,12 +20,20 @@ profiles/oneoff_spread.json).
                   there, the host layer splits) and on, --runs fresh schedulers each; then the PLAIN instance on a cluster made of
                   just the pool's nodes, knob on: the difference is the cost of compaction (probe, gather, base sums, indirection).
                   e.g. --pool --out profiles/oneoff_spread_compact.json
+  --riders      with --pool: after every --riders-every (50) pooled spread tasks come --riders-count (10) UNCONSTRAINED plain one-off
+                  tasks. The one spread segment of the tick then has the whole nodeSet as its union; the preparation cuts it
+                  (csrc/swp_scan_spread.hpp k_spread_cut) into a spread segment per run with a stretch of the block resolver per gap.
+                  Knob off (what the parent commit does with this tick, knob on or off) against knob on, --runs each; the
+                  preparation's share — first probe, cut, second probe — from the engine's own SWP_DEBUG_PREPARE line.
+                  e.g. --pool --riders --out profiles/oneoff_spread_cut.json
 
 usage: python tools/bench_oneoff_spread.py [--tasks 20000] [--services 200] [--nodes 1000] [--zones 5] [--runs 3] [--out FILE]
-       python tools/bench_oneoff_spread.py --pool [--pool-nodes 10000] [--pool-every 10] [--tasks 20000] [--services 200] [--runs 3] [--out FILE]"""
+       python tools/bench_oneoff_spread.py --pool [--pool-nodes 10000] [--pool-every 10] [--tasks 20000] [--services 200] [--runs 3] [--out FILE]
+       python tools/bench_oneoff_spread.py --pool --riders [--riders-every 50] [--riders-count 10] [--runs 3] [--out FILE]"""
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 import time
@@ -86,8 +94,14 @@ def pool_node_doc(i, zones, every):
             "Description": {"Resources": {"NanoCPUs": 64 * 10**9, "MemoryBytes": 256 << 30}}}
 
 
+def rider_doc(j, services):
+    return {"ID": "t%06d" % j, "ServiceID": "svc%03d" % (j % services), "DesiredState": RUNNING, "Status": {"State": PENDING},
+            "Spec": {"Resources": {"Reservations": {"NanoCPUs": 10**8, "MemoryBytes": 64 << 20}}}}
+
+
 def pool_tick(a, knob, only_pool, profile=False):
-    """one tick of --tasks pooled spread tasks; only_pool: the cluster is just the pool's nodes (the plain instance)"""
+    """one tick of --tasks pooled spread tasks; only_pool: the cluster is just the pool's nodes (the plain instance);
+    --riders: unconstrained plain tasks between runs of them (ids in creation order)"""
     if knob:
         os.environ[KNOB] = "1"
     else:
@@ -98,17 +112,81 @@ def pool_tick(a, knob, only_pool, profile=False):
             s.create_node(pool_node_doc(i, a.zones, a.pool_every))
     for k in range(a.services):
         s.set_service("svc%03d" % k)
+    at = 0
     for j in range(a.tasks):
-        t = task_doc(j, a.services)
+        t = task_doc(at, a.services)
         t["Spec"]["Placement"]["Constraints"] = ["node.labels.pool==a"]
         s.create_task(t)
+        at += 1
+        if getattr(a, "riders", False) and (j + 1) % a.riders_every == 0 and j + 1 < a.tasks:
+            for _ in range(a.riders_count):
+                s.create_task(rider_doc(at, a.services))
+                at += 1
     t0 = time.perf_counter()
     d = s.tick()
     ms = (time.perf_counter() - t0) * 1e3
     return ms, {x["ID"]: x["NodeID"] for x in d}, s.e.stats()
 
 
+def prepare_lines(a):
+    """one more knob-on tick with SWP_DEBUG_PREPARE set and the process's stderr in a file: the engine's own lines about the preparation"""
+    path = (a.out or "/tmp/bench_oneoff_spread") + ".stderr"
+    sys.stderr.flush()
+    keep, fd = os.dup(2), os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    os.dup2(fd, 2)
+    os.environ["SWP_DEBUG_PREPARE"] = "1"
+    try:
+        pool_tick(a, True, False)
+    finally:
+        os.environ.pop("SWP_DEBUG_PREPARE", None)
+        os.dup2(keep, 2)
+        os.close(fd)
+        os.close(keep)
+    text = open(path).read()
+    os.remove(path)
+    out = {}
+    m = re.search(r"spread cut: (\d+) of (\d+) segments too wide, limit (\d+) nodes: (\d+) segments now; first probe ([\d.]+) ms, cut ([\d.]+) ms, second probe ([\d.]+) ms", text)
+    if m:
+        out = {"segments_too_wide": int(m.group(1)), "segments_before": int(m.group(2)), "limit_nodes": int(m.group(3)), "segments_after": int(m.group(4)),
+               "first_probe_ms": float(m.group(5)), "cut_ms": float(m.group(6)), "second_probe_ms": float(m.group(7))}
+    m = re.search(r"swp_batch_prepare (\d+) tasks: build ([\d.]+) ms, upload ([\d.]+) ms", text)
+    if m:
+        out.update(prepare_build_ms=float(m.group(2)), prepare_upload_and_probes_ms=float(m.group(3)))
+    return out
+
+
+def riders_main(a):
+    os.environ["SWP_HOST"] = "cxx"
+    one_tick(argparse.Namespace(nodes=64, zones=a.zones, services=4, tasks=64), True)   # warm: modules, pools
+    n_runs = (a.tasks + a.riders_every - 1) // a.riders_every
+    off, on, want, st_on = [], [], None, None
+    for r in range(a.runs):
+        for knob in ((False, True) if r % 2 == 0 else (True, False)):
+            ms, dec, st = pool_tick(a, knob, False)
+            (on if knob else off).append(ms)
+            if want is None:
+                want = dec
+            assert dec == want, "the two paths decide the tick differently"
+            if knob:
+                assert st["scan_tasks"] >= a.tasks and st["scan_launches"] >= n_runs, st
+                st_on = st
+    ms, _, st = pool_tick(a, True, False, profile=True)
+    eng = {"tick_ms_with_profile": round(ms, 3), "spread_segments_ms": round(st["ms_scan"], 3), "batch_ms_total": round(st["ms_total"], 3)}
+    out = {"tool": "bench_oneoff_spread --pool --riders", "spread_tasks": a.tasks, "riders": len(want) - a.tasks, "riders_every": a.riders_every, "riders_count": a.riders_count,
+           "services": a.services, "nodes": a.pool_nodes, "pool_nodes": len(range(0, a.pool_nodes, a.pool_every)), "zones": a.zones, "runs": a.runs,
+           "placed": sum(1 for v in want.values() if v), "spread_runs": n_runs,
+           "knob_on_counters": {k: st_on[k] for k in ("batches", "scan_launches", "scan_tasks", "resolve_launches")},
+           "tick_ms": {"knob_off_parent_path": summary(off), "knob_on_cut": summary(on), "off_over_on_median": round(statistics.median(off) / statistics.median(on), 2)},
+           "engine_knob_on": eng, "preparation_knob_on": prepare_lines(a)}
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
 def pool_main(a):
+    if a.riders:
+        return riders_main(a)
     os.environ["SWP_HOST"] = "cxx"
     one_tick(argparse.Namespace(nodes=64, zones=a.zones, services=4, tasks=64), True)   # warm: modules, pools
     off, on, plain, want = [], [], [], None
@@ -174,6 +252,9 @@ def main():
     ap.add_argument("--pool", action="store_true", help="the compact form: a labelled pool of a cluster beyond 4 096 nodes")
     ap.add_argument("--pool-nodes", type=int, default=10_000)
     ap.add_argument("--pool-every", type=int, default=10)
+    ap.add_argument("--riders", action="store_true", help="with --pool: unconstrained plain one-off tasks between runs of the pooled spread tasks (the segment is cut)")
+    ap.add_argument("--riders-every", type=int, default=50)
+    ap.add_argument("--riders-count", type=int, default=10)
     a = ap.parse_args()
     if a.pool:
         return pool_main(a)
