@@ -326,7 +326,14 @@ typedef struct {
  *     limit; a task without preferences found there goes, with the plain tasks behind it, to the block / scan resolver, and the
  *     next piece starts at the next task with preferences. Cutting is exact: the pieces decide the tasks in array order. What stays
  *     refused is a task with preferences whose OWN class row has more than 4 096 nodes (and a segment of more than 4 096 pieces):
- *     with the message of the segment as a whole;
+ *     with the message of the segment as a whole. With SWP_SPREAD_WIDE=1 in the environment when the engine is created (off by
+ *     default) such a segment is not refused either: it keeps its shape and runs whole — the pooled and plain tasks that ride in it
+ *     included — through the WIDE instance (k_scan_spread_wide), which decides over ALL node slots with the node rows in global
+ *     memory: the service with `spread=node.labels.zone` and no constraint on a cluster of 10 000 nodes. Its own limits, refused in
+ *     the same way: a nodeSet of at most 65 536 node slots (the key's 16 bits for the node); the two (service, node) matrices,
+ *     services x node slots x 8 bytes, at most 1 GiB; the trees' words (no node rows next to them) within the LDS; and a node that
+ *     holds 65 536 tasks or more fails the batch with SWP_ERANGE in front of the first task that could take it. A wide segment is
+ *     never refused for its width when the batch runs;
  *   - the node rows (24 bytes a slot, or a node of the largest union) and the trees of the batch's spread sets — 32 bytes per branch
  *     of the largest tree, 20 per branch of all of them, 32 per level — fit 160 KiB - 512 bytes of LDS (4 096 nodes leave room for
  *     some 1 200 branches);

@@ -468,7 +468,7 @@ struct swp_batch {
     DevBuf d_thr64, d_planes6, d_rr6, d_blk6;   // k_resolve6: raw thresholds, level planes, demand-class rows, control block
     // segments of the batch: runs of identical tasks (k_waterfill) and the stretches between them (the resolvers)
     // ... and the spread segments (k_scan_spread, swp_rounds.hpp spread_segments): one-off tasks with spread preferences, one after the other
-    struct Seg { uint32_t j0, n; bool run; bool spread = false; };
+    struct Seg { uint32_t j0, n; bool run; bool spread = false; bool wide = false; };   // wide: a spread segment the WIDE instance decides (k_scan_spread_wide, SWP_SPREAD_WIDE=1)
     std::vector<Seg> segs;
     // one-off tasks with spread preferences: sp_tree[task] = the task's tree among sp_sets' (tree 0 = spread set 0: no levels, one leaf);
     // the trees themselves are built from the host mirror when the batch RUNS (labels may have moved since it was prepared)
@@ -597,6 +597,7 @@ struct swp_engine {
     std::vector<hipEvent_t> ev_scan;   // SWP_CFG_PROFILE: a pair per stretch the scan resolver took (scan_stretch); ev_scan_used of them in this batch
     uint32_t ev_scan_used = 0, scan_tasks_batch = 0, scan_stretches_batch = 0;
     uint32_t scan_batched_batch = 0, scan_skipped_batch = 0;   // ... of them by k_scanb; tasks it answered without a look
+    bool spread_wide = false;       // SWP_SPREAD_WIDE=1, read once at swp_create: a compact spread segment that is too wide and cannot be cut runs whole through k_scan_spread_wide instead of being refused
     bool r6_compact_hint = false;   // the last batch's rounds used a compact index (re-placements after a drain): the next one starts with it
     swp_stats_t stats{};
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -2210,6 +2211,23 @@ int scan_stretch(swp_engine* e, swp_batch* b, const R6Run& run, const R6Args& ra
 // but the batch's own probe buffers. The unions themselves are built again, segment by segment, when the segments run (the scan
 // stretches in between share the buffers).
 // the limit over the counts in b->sp_nc. wide: instead of refusing, the positions in b->segs of the segments beyond it
+// The wide instance's own limits (k_scan_spread_wide, SWP_SPREAD_WIDE=1), checked wherever a segment becomes or stays wide: the key's 16
+// bits for the node, the two (service, node) matrices over ALL node slots, the trees' words in LDS. Refuses with nothing written.
+constexpr size_t SPREAD_WIDE_MATRIX_BYTES = (size_t)1 << 30;   // hmat + emat: n_svc x n_nodes x 8 bytes (200 services on 65 536 nodes: 100 MiB)
+int spread_wide_limits(swp_engine* e, swp_batch* b) {
+    const SpreadTrees& t = b->sp_trees;
+    if (e->n_nodes > scan_spread_wide_max_nodes())
+        return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (the wide spread kernel takes a nodeSet of at most %u node slots: this one has %u)",
+                       scan_spread_wide_max_nodes(), e->n_nodes);
+    if ((size_t)b->n_svc * e->n_nodes * 8 > SPREAD_WIDE_MATRIX_BYTES)
+        return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (the wide spread kernel's matrices of %u services over %u node slots, %zu bytes, exceed %zu)",
+                       b->n_svc, e->n_nodes, (size_t)b->n_svc * e->n_nodes * 8, SPREAD_WIDE_MATRIX_BYTES);
+    if (scan_spread_wide_lds_size(t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) > R6_LDS_BUDGET)
+        return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (trees of %u branches, the largest of %u over %u levels, exceed the wide spread kernel's LDS)",
+                       t.tree_off.back(), t.max_ntn, t.max_depth);
+    return SWP_OK;
+}
+
 int spread_limit(swp_engine* e, swp_batch* b, std::vector<uint32_t>* wide) {
     const SpreadTrees& t = b->sp_trees;
     uint32_t k = 0;
@@ -2217,7 +2235,8 @@ int spread_limit(swp_engine* e, swp_batch* b, std::vector<uint32_t>* wide) {
         const swp_batch::Seg& sg = b->segs[i];
         if (!sg.spread) continue;
         const uint32_t nc = b->sp_nc[k++];
-        const bool fits = scan_spread_lds_size(nc, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) <= R6_LDS_BUDGET;
+        if (sg.wide) continue;   // (the wide instance runs over all node slots: no union, no width to refuse)
+        const bool fits =scan_spread_lds_size(nc, t.max_ntn, t.max_depth, (uint32_t)b->sp_sets.size(), t.tree_off.back()) <= R6_LDS_BUDGET;
         if (wide && (nc > scan_max_nodes() || !fits)) { wide->push_back((uint32_t)i); continue; }
         if (nc > scan_max_nodes())
             return e->fail(SWP_EUNSUPPORTED, "a task has spread preferences: schedule it through swp_schedule_groups (a batch takes them where the nodes its segment's tasks can use number at most %u: the union of the class rows of segment %u, tasks [%u, %u), has %u of this nodeSet's %u)",
@@ -2244,11 +2263,15 @@ int spread_probe(swp_engine* e, swp_batch* b, std::vector<uint32_t>* wide = null
     sa.n_sc = b->n_sc;
     if (int rc = scan_compact_bufs(e, b, &sa)) return rc;
     uint32_t k = 0;
+    bool any_wide = false;
+    for (const swp_batch::Seg& sg : b->segs) any_wide = any_wide || (sg.spread && sg.wide);
+    if (any_wide) HIPCHECK(e, hipMemsetAsync(b->d_sp_cnc.p, 0, (size_t)n_seg * 4, e->stream));   // (a wide segment keeps its word, never probed: 0)
     for (const swp_batch::Seg& sg : b->segs) {
         if (!sg.spread) continue;
         sa.j0 = sg.j0;
         sa.j1 = sg.j0 + sg.n;
         sa.cnc = b->d_sp_cnc.as<uint32_t>() + k++;
+        if (sg.wide) continue;
         const hipError_t r = launch_scan_probe(sa, e->stream);   // (zeroes cused in front of the marks)
         if (r != hipSuccess) return e->fail(SWP_EHIP, "k_scan_union launch: %s", hipGetErrorString(r));
     }
@@ -2266,9 +2289,17 @@ constexpr uint32_t SPREAD_CUT_PIECES = 4096;
 int spread_cut(swp_engine* e, swp_batch* b, const std::vector<uint32_t>& wide, double first_probe_ms) {
     const std::vector<swp_batch::Seg> segs0 = b->segs;
     const std::vector<uint32_t> nc0 = b->sp_nc;
+    // SWP_SPREAD_WIDE=1: a segment that cannot be cut is not refused — it keeps the shape spread_segments gave it and runs whole through
+    // the wide instance (whichever instance decides its pooled and plain tasks, the answer is exact), within that instance's own limits
+    bool wide_checked = false;
     auto refuse = [&]() {
         b->segs = segs0;
         b->sp_nc = nc0;
+        if (e->spread_wide) {   // (nothing could be cut: every segment that is too wide becomes wide)
+            if (int rc = spread_wide_limits(e, b)) return rc;
+            for (uint32_t i : wide) b->segs[i].wide = true;
+            return (int)SWP_OK;
+        }
         return spread_limit(e, b, nullptr);
     };
     const bool dbg = getenv("SWP_DEBUG_PREPARE") != nullptr;
@@ -2325,7 +2356,17 @@ int spread_cut(swp_engine* e, swp_batch* b, const std::vector<uint32_t>& wide, d
     for (size_t i = 0; i < segs0.size(); ++i) {
         if (q == wide.size() || wide[q] != i) { push(segs0[i]); continue; }
         const uint32_t* o = lists.data() + off[q++];
-        if (o[0] != CUT_OK) return refuse();
+        if (o[0] != CUT_OK) {   // CUT_OWN_ROW, CUT_FULL
+            if (!e->spread_wide) return refuse();
+            if (!wide_checked) {
+                if (int rc = spread_wide_limits(e, b)) { b->segs = segs0; b->sp_nc = nc0; return rc; }
+                wide_checked = true;
+            }
+            swp_batch::Seg sg = segs0[i];
+            sg.wide = true;
+            cut.push_back(sg);
+            continue;
+        }
         uint32_t at = segs0[i].j0;
         for (uint32_t k = 0; k < o[2]; ++k) {
             const uint32_t* pc = o + CUT_HEAD + 3 * k;
@@ -2367,6 +2408,12 @@ int spread_tables(swp_engine* e, swp_batch* b) {
     const SpreadTrees& t = b->sp_trees;
     if (b->sp_compact) {
         int rc;
+        // (a wide segment is never refused for its width here: the probe skips it. Its trees are this run's: their words against the LDS)
+        for (const swp_batch::Seg& sg : b->segs)
+            if (sg.spread && sg.wide) {
+                if ((rc = spread_wide_limits(e, b))) return rc;
+                break;
+            }
         if ((rc = spread_probe(e, b))) return rc;
         if ((rc = upload(e, b->d_sp_pair, b->sp_pair))) return rc;
         if ((rc = upload(e, b->d_sp_psvc, b->sp_pair_svc))) return rc;
@@ -2391,7 +2438,7 @@ int spread_tables(swp_engine* e, swp_batch* b) {
 // and the logs come out as the scan resolver leaves them; the block resolver's bitmaps are NOT rebuilt here — a stretch of rounds
 // behind the segment builds them from the node rows when it begins (stretch_begin), a k_waterfill run reads none — so a batch that is
 // all spread segments never meets the block resolver's limit on the nodes' task-count spread. Streamed: a publish behind the segment.
-int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_t j1, uint32_t seg_index) {
+int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_t j1, uint32_t seg_index, bool wide = false) {
     hipStream_t st = e->stream;
     R6Args ra{};
     if (int rc = r6_args_for(e, b, run.largest(), run.task_rows, run.knobs, &ra)) return rc;
@@ -2404,7 +2451,9 @@ int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_
     sa.n_sc = b->n_sc;
     // compact: the union of the segment's class rows into the batch's compact buffers (shared with the scan stretches: built again
     // here), its node count as spread_tables' probe of this run read it — the class rows do not move inside a run
-    const bool cm = b->sp_compact;
+    // wide (SWP_SPREAD_WIDE=1): a segment of a compact batch that runs over ALL node slots — the matrices of the plain instance, the
+    // node rows in global memory (k_scan_spread_wide): no union, no pairs, no base sums
+    const bool cm = b->sp_compact && !wide;
     const uint32_t n_c = cm ? b->sp_nc[seg_index] : 0u;
     const size_t cols = cm ? std::max<uint32_t>(n_c, 1u) : e->n_nodes;
     HIPCHECK(e, b->d_hmat.reserve((size_t)b->n_svc * cols * 4));
@@ -2438,7 +2487,7 @@ int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_
     hipError_t r;
     if (!cm) {
         r = launch_scan_matrices(sa, st);
-        if (r == hipSuccess) r = launch_scan_spread(sp, st, e->device);
+        if (r == hipSuccess) r = wide ? launch_scan_spread_wide(sp, st, e->device) : launch_scan_spread(sp, st, e->device);
     } else {
         r = launch_scan_probe(sa, st);
         if (r == hipSuccess) r = launch_scan_matrices_compact(sa, st);
@@ -2456,11 +2505,13 @@ int spread_segment(swp_engine* e, swp_batch* b, R6Run& run, uint32_t j0, uint32_
     Blk6 hb{};
     if (int rc = read_back(e, b, run.sx, b->d_blk6.p, &hb, sizeof hb)) return rc;
     if (hb.error == ERR_GROUP_RANGE) return e->fail(SWP_ERANGE, "a node's key left its range (>= 256 recent failures or >= 2^24 tasks of one service on a node)");
+    if (hb.error == ERR_LEVEL_RANGE && wide) return e->fail(SWP_ERANGE, "a node holds 65536 tasks or more: beyond the wide spread kernel's packed key (the segment stopped in front of task %u)", hb.pos);
     if (hb.error == ERR_LEVEL_RANGE) return e->fail(SWP_ERANGE, "a node holds 2^20 tasks or more: beyond the scan resolver's packed key");
     if (hb.error != ERR_NONE) return e->fail(SWP_EHIP, "k_scan_spread: the walk of a task did not end within its bound (error %u)", hb.error);
     if (hb.pos != j1) return e->fail(SWP_EHIP, "k_scan_spread stopped at task %u of [%u, %u)", hb.pos, j0, j1);
     if (run.knobs.dbg & 16) {
-        if (cm) fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u) over a union of %u of %u nodes, %u (service, tree) pairs: trees of at most %u branches over %u levels\n", j0, j1, n_c, e->n_nodes, sp.n_pairs, sp.max_ntn, sp.max_depth);
+        if (wide) fprintf(stderr, "[swp] k_scan_spread_wide decided tasks [%u, %u) over all %u node slots: trees of at most %u branches over %u levels\n", j0, j1, e->n_nodes, sp.max_ntn, sp.max_depth);
+        else if (cm) fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u) over a union of %u of %u nodes, %u (service, tree) pairs: trees of at most %u branches over %u levels\n", j0, j1, n_c, e->n_nodes, sp.n_pairs, sp.max_ntn, sp.max_depth);
         else fprintf(stderr, "[swp] k_scan_spread decided tasks [%u, %u): trees of at most %u branches over %u levels\n", j0, j1, sp.max_ntn, sp.max_depth);
     }
     return SWP_OK;
@@ -2693,7 +2744,7 @@ int batch_run_impl(swp_engine* e, swp_batch* b, StreamRun* sx) {
         uint32_t spread_seen = 0;
         for (const swp_batch::Seg& sg : b->segs) {
             if (sg.spread) {
-                if ((rc = spread_segment(e, b, run, sg.j0, sg.j0 + sg.n, spread_seen++))) break;
+                if ((rc = spread_segment(e, b, run, sg.j0, sg.j0 + sg.n, spread_seen++, sg.wide))) break;
                 continue;
             }
             if (!sg.run) {
@@ -3251,6 +3302,7 @@ int swp_create(const swp_config* cfg, swp_engine** out) {
     for (int s = 0; s < SWP_SPACE_COUNT; ++s) e->spaces[s].init(s != SWP_SPACE_NODE_ID);
     e->role_worker = e->spaces[SWP_SPACE_FOLDED].get("worker");
     e->role_manager = e->spaces[SWP_SPACE_FOLDED].get("manager");
+    if (const char* w = getenv("SWP_SPREAD_WIDE")) e->spread_wide = atoi(w) == 1;
     *out = e.release();
     return SWP_OK;
 }

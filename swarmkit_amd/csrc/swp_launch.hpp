@@ -70,6 +70,10 @@ hipError_t launch_scan_spread(const SpreadArgs& p, hipStream_t st, int dev);    
 hipError_t launch_scan_matrices_compact(const ScanArgs& s, hipStream_t st);     // k_scan_fill_c + k_scan_lists_c alone: the matrices over the union's s.n_c columns (behind launch_scan_probe)
 // the compact spread instance, behind launch_scan_probe + launch_scan_matrices_compact: k_spread_base (the pairs' leaf sums over the nodes outside the union) + k_scan_spread<.., true>
 hipError_t launch_scan_spread_compact(const SpreadArgs& p, const uint32_t* pair_svc, const uint32_t* pair_tree, uint32_t* base, hipStream_t st, int dev);
+// the wide spread instance (k_scan_spread_wide): all node slots of a nodeSet beyond scan_max_nodes(), the node rows in global memory
+size_t scan_spread_wide_lds_size(uint32_t max_ntn, uint32_t max_depth, uint32_t n_trees, uint32_t tot_ntn);   // its LDS: no node rows
+uint32_t scan_spread_wide_max_nodes();                                               // SPREAD_WIDE_MAXN: the key's 16 bits for the node
+hipError_t launch_scan_spread_wide(const SpreadArgs& p, hipStream_t st, int dev);    // behind launch_scan_matrices
 // a compact spread segment whose union is too wide: the pieces to cut it into (k_spread_cut, swp_scan_spread.hpp), one workgroup
 struct CutArgs;
 hipError_t launch_spread_cut(CutArgs p, hipStream_t st, int dev);

@@ -53,6 +53,19 @@ hipError_t launch_scan_spread_compact(const SpreadArgs& p, const uint32_t* pair_
     }
 }
 
+// ---- the wide instance: all node slots of a nodeSet beyond SCAN_MAXN, the node rows in global memory (k_scan_spread_wide)
+size_t scan_spread_wide_lds_size(uint32_t max_ntn, uint32_t max_depth, uint32_t n_trees, uint32_t tot_ntn) { return scan_lds_spw(max_ntn, max_depth, n_trees, tot_ntn); }
+uint32_t scan_spread_wide_max_nodes() { return SPREAD_WIDE_MAXN; }
+// the tasks [p.s.j0, p.s.j1) one after the other; p.s.hmat / emat as launch_scan_matrices left them, over all nodes
+hipError_t launch_scan_spread_wide(const SpreadArgs& p, hipStream_t st, int dev) {
+    const size_t lds = scan_lds_spw(p.max_ntn, p.max_depth, p.n_trees, p.tot_ntn);
+    if (p.s.a.n_nodes == 0 || p.s.a.n_nodes > SPREAD_WIDE_MAXN || lds > (size_t)160 * 1024 - 512) return hipErrorInvalidValue;
+    hipError_t r;
+    if (lds > 48 * 1024 && (r = ensure_big_lds(reinterpret_cast<const void*>(&k_scan_spread_wide), dev)) != hipSuccess) return r;
+    hipLaunchKernelGGL(k_scan_spread_wide, dim3(1), dim3(SCAN_THREADS), lds, st, p);
+    return hipGetLastError();
+}
+
 // ---- a compact segment too wide for the kernel: where to cut it (k_spread_cut), one workgroup
 // the piece's union in LDS where it fits next to the flags, else in p.cu; hipErrorInvalidValue: not even the flags fit (the caller refuses)
 hipError_t launch_spread_cut(CutArgs p, hipStream_t st, int dev) {

@@ -536,4 +536,218 @@ WV_KERNEL(SCAN_THREADS) void k_scan_spread(SpreadArgs p) {
 }
 #endif   // SWP_SCAN_SPREAD_KERNEL
 
+// The WIDE instance: k_scan_spread<.., false>'s semantics over ALL a.n_nodes slots of a nodeSet beyond SCAN_MAXN — the task with
+// preferences and no constraint, whose own class row holds every ready node. What stops the plain instance is where it keeps its state:
+// here the node rows (cpu, mem, total, last) STAY in global memory, read and written in place by their owner (thread tid owns the nodes
+// tid, tid + SCAN_THREADS, ... — up to 64 of them: `present` is one bit a node), so there is no prologue copy and no epilogue copy, and
+// LDS holds only the result words, the two sets of per-tree words, the frames and the trees' tables (scan_lds_spw). No per-node copies
+// of the next task's words either: the class word, the hmat cell, the leaf and the row of a node are read inside the loop over the
+// thread's nodes, SPW_U nodes at a time so that the loads of SPW_U iterations are in flight together; only the three words that say
+// where a task's data lies (sc, svc, tree) are requested two tasks ahead. A plain thread issues up to four LDS atomics a task, a wide
+// one would issue up to 64 on a handful of leaf words: the running sum and the least key are FOLDED in registers while consecutive
+// nodes of the thread fall into the same leaf, and an atomic is issued only when the leaf changes and at the loop's end (exact: min and
+// add are associative and the key carries the node). The key is hi << 32 | total << 16 | node: SPREAD_WIDE_MAXN = 65 536 slots, and a
+// feasible node that holds 65 536 tasks or more raises ERR_LEVEL_RANGE and STOPS the segment in front of the task (a word in LDS, read
+// by everybody behind the task's first barrier: the trip count stays uniform) — never a wrong pick. No base sums: nothing lies outside
+// the node range (tpair / base stay null).
+#define SPREAD_WIDE_MAXN 65536u
+#define SPW_U 4
+// two result words, the stop word + two sets of (leafmin, tsum, noroom) per tree node of the largest tree + a frame per level + the tables
+inline __host__ __device__ size_t scan_lds_spw(u32 max_ntn, u32 max_depth, u32 n_trees, u32 tot_ntn) {
+    return 32 + (size_t)2 * max_ntn * 16 + (size_t)(max_depth + 1) * sizeof(SpFrame) + ((size_t)n_trees + 1 + (size_t)5 * tot_ntn) * 4;
+}
+
+#ifdef SWP_SCAN_SPREAD_KERNEL
+WV_KERNEL(SCAN_THREADS) void k_scan_spread_wide(SpreadArgs p) {
+    const ScanArgs& s = p.s;
+    const R6Args& a = s.a;
+    const u32 tid = wv::tid(), lane = wv::lane(), N = a.n_nodes, Wn = a.n_words, M = p.max_ntn;
+    u64* res = wv::lds();                                  // [2] the walk's answer, alternating; [2]: != 0 stops the segment
+    u64* lmin = res + 4;                                   // [2][M] a leaf's least key
+    u32* lsum = reinterpret_cast<u32*>(lmin + 2 * (size_t)M);   // [2][M] tree.tasks
+    u32* lnor = lsum + 2 * (size_t)M;                      // [2][M] noRoom
+    SpFrame* frames = reinterpret_cast<SpFrame*>(lnor + 2 * (size_t)M);   // [max_depth + 1]
+    u32* l_off = reinterpret_cast<u32*>(frames + p.max_depth + 1);       // [n_trees + 1] tree_off
+    u32* l_parent = l_off + p.n_trees + 1;                                // [tot_ntn] each: the trees' tables
+    u32* l_first = l_parent + p.tot_ntn;
+    u32* l_next = l_first + p.tot_ntn;
+    u32* l_nchild = l_next + p.tot_ntn;
+    u32* l_depth = l_nchild + p.tot_ntn;
+    if (a.blk->error != ERR_NONE) return;
+    const u32 last = s.j0 < s.j1 ? s.j1 - 1u : 0u, first = s.j0 < s.j1 ? s.j0 : 0u;   // (reads beyond the stretch are clamped to its last task and never used)
+    const u32 second = s.j0 + 1u < s.j1 ? s.j0 + 1u : last;
+    for (u32 i = tid; i < 2 * M; i += SCAN_THREADS) { lmin[i] = KEY_NONE; lsum[i] = 0; lnor[i] = 0; }
+    if (tid == 0) res[2] = 0;
+    for (u32 i = tid; i <= p.n_trees; i += SCAN_THREADS) l_off[i] = p.tree_off[i];
+    for (u32 i = tid; i < p.tot_ntn; i += SCAN_THREADS) {
+        l_parent[i] = p.tn_parent[i]; l_first[i] = p.tn_first[i]; l_next[i] = p.tn_next[i]; l_nchild[i] = p.tn_nchild[i]; l_depth[i] = p.tn_depth[i];
+    }
+    const u32 nq = (N + SCAN_THREADS - 1u) / SCAN_THREADS;   // nodes of the thread with the most (<= 64: the launcher refuses more slots)
+    u64 present = 0;   // bit q: this thread's q-th node exists and is in the nodeSet
+    for (u32 q = 0; q < nq; ++q) {
+        const u32 n = tid + q * SCAN_THREADS;
+        if (n < N && ((a.valid[n >> 6] >> (n & 63)) & 1ull)) present |= 1ull << q;
+    }
+    u32 nc = a.ctl->ncommit, ni = a.ctl->ninf;
+    u32 sc_n = a.rt[first].sc, svc_n = a.rt[first].svc, tree_n = p.ttree[first];
+    u32 sc_nn = a.rt[second].sc, svc_nn = a.rt[second].svc, tree_nn = p.ttree[second];
+    const u32* sc32 = reinterpret_cast<const u32*>(a.sc);   // (the class word as the 32-bit half that holds the node's bit)
+    wv::barrier();
+    u32 t = s.j0;
+    for (; t < s.j1; ++t) {
+        const RTask r = a.rt[t];
+        const u32 set = (t - s.j0) & 1u, tree = tree_n, tbase = l_off[tree], ntn = l_off[tree + 1] - tbase;
+        const u32 sc_t = sc_n, svc_t = svc_n;
+        u64* leafmin = lmin + (size_t)set * M;
+        u32* tsum = lsum + (size_t)set * M;
+        u32* noroom = lnor + (size_t)set * M;
+        const u32 gset = a.n_rg ? a.tg[t] : 0u;
+        const bool with_res = (r.flags & RT_RES) != 0;
+        // the next task's set (last read by the walk two tasks ago, in front of that task's second barrier)
+        for (u32 i = tid; i < M; i += SCAN_THREADS) { lmin[(size_t)(set ^ 1u) * M + i] = KEY_NONE; lsum[(size_t)(set ^ 1u) * M + i] = 0; lnor[(size_t)(set ^ 1u) * M + i] = 0; }
+        // the words that say where the tasks behind this one lie: they have this task's whole turn to arrive
+        sc_n = sc_nn;
+        svc_n = svc_nn;
+        tree_n = tree_nn;
+        {
+            const u32 t2 = t + 2 < s.j1 ? t + 2 : last;
+            sc_nn = a.rt[t2].sc;
+            svc_nn = a.rt[t2].svc;
+            tree_nn = p.ttree[t2];
+        }
+        // ---- every thread: its nodes into their leaves, SPW_U at a time; the fold runs across the groups
+        const u32* scrow = sc32 + (size_t)sc_t * Wn * 2u;
+        const u32* hrow = s.hmat + (size_t)svc_t * N;
+        const u32* lrow = p.leaf_of_node + (size_t)tree * N;
+        u32 cur = 0, acc = 0;   // the leaf of the fold, its sum so far ...
+        u64 best = KEY_NONE;    // ... and its least key so far
+        for (u32 q0 = 0; q0 < nq; q0 += SPW_U) {
+            const u32 pm = (u32)(present >> q0) & ((1u << SPW_U) - 1u);
+            if (!pm) continue;
+            u32 scw[SPW_U], hiv[SPW_U], lfv[SPW_U], ttv[SPW_U];
+            i64 cpv[SPW_U], mmv[SPW_U];
+            WV_UNROLL
+            for (int i = 0; i < SPW_U; ++i) {
+                const u32 n = tid + (q0 + (u32)i) * SCAN_THREADS;
+                const bool in = (pm >> i) & 1u;
+                scw[i] = in ? scrow[n >> 5] : 0u;
+                hiv[i] = in ? hrow[n] : 0u;
+                lfv[i] = in ? lrow[n] : LIST_EMPTY;
+                ttv[i] = in ? a.total[n] : 0u;
+                cpv[i] = in && with_res ? a.cpu[n] : 0;
+                mmv[i] = in && with_res ? a.mem[n] : 0;
+            }
+            WV_UNROLL
+            for (int i = 0; i < SPW_U; ++i) {
+                if (!((pm >> i) & 1u)) continue;
+                const u32 n = tid + (q0 + (u32)i) * SCAN_THREADS, w = n >> 6;
+                const u64 bit = 1ull << (n & 63);
+                const u32 hi = hiv[i], lf = lfv[i];
+                if (lf >= ntn) continue;   // (tables of another nodeSet: the launcher builds them from the one the batch was prepared for)
+                if (lf != cur) {           // the leaf changes: what the fold holds goes to LDS
+                    if (acc) wv::lds_add32(tsum + cur, acc);
+                    if (best != KEY_NONE) wv::lds_min64(leafmin + cur, best);
+                    cur = lf;
+                    acc = 0;
+                    best = KEY_NONE;
+                }
+                acc += hi & 0xFFFFFFu;     // tree.tasks: every node of the nodeSet, feasible or not
+                if (!((scw[i] >> (n & 31u)) & 1u)) continue;   // (the static class row holds valid & ready & constraints & platform & plugins)
+                if (with_res && !(r.cpu <= cpv[i] && r.mem <= mmv[i])) continue;
+                bool ok = true;
+                if (gset)
+                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) {
+                        const u32 row = a.gs_row[g];
+                        if (a.gcnt[(size_t)a.rg_kind[row] * a.gstride + n] < a.rg_val[row]) ok = false;   // HasEnough, validate.go:24-52
+                    }
+                if (ok && (r.flags & RT_PORTS))
+                    for (u32 z = a.pset_off[r.pset]; z < a.pset_off[r.pset + 1]; ++z)
+                        if (wv::g_fresh64(a.portmap + (size_t)a.pset_ids[z] * Wn + w) & bit) ok = false;
+                if (ok && (r.flags & RT_MAXREP) && !((u64)(hi & 0xFFFFFFu) < r.maxrep)) ok = false;
+                if (!ok) continue;
+                const u32 tn = ttv[i];
+                if (tn >> 16) {   // beyond the 16 bits the key has for the count: the segment stops in front of this task
+                    a.blk->error = ERR_LEVEL_RANGE;
+                    res[2] = 1;
+                    continue;
+                }
+                const u64 key = ((u64)hi << 32) | ((u64)tn << 16) | n;
+                if (key < best) best = key;
+            }
+        }
+        if (acc) wv::lds_add32(tsum + cur, acc);
+        if (best != KEY_NONE) wv::lds_min64(leafmin + cur, best);
+        wv::barrier();
+        if (wv::lds_read64(res + 2)) break;   // (written in front of the barrier only, never cleared: uniform)
+        // ---- wave 0: the sums up the tree, a level at a time from the deepest (a child's sum is complete before it is added), then the walk
+        if (tid < 64) {
+            for (u32 d = p.max_depth; d >= 1; --d) {
+                for (u32 i = lane; i < ntn; i += 64)
+                    if (l_depth[tbase + i] == d && tsum[i]) wv::lds_add32(tsum + l_parent[tbase + i], tsum[i]);
+                wv::wave_sync();
+                wv::lockstep();
+            }
+            if (lane == 0) {
+                bool hang = false;
+                res[set] = spread_walk(l_first + tbase, l_next + tbase, l_nchild + tbase, p.max_depth, ntn, leafmin, tsum, noroom, frames, &hang);
+                if (hang) a.blk->error = ERR_SPREAD_WALK;
+            }
+        }
+        wv::barrier();
+        const u64 gk = wv::lds_read64(res + set);
+        const u32 gn = gk == KEY_NONE ? R6_NONE : (u32)gk & (SPREAD_WIDE_MAXN - 1u);
+        // ---- the owner of the node applies the placement (NodeInfo.addTask), on the node's row in global memory; everybody counts
+        if (gn == R6_NONE) {
+            if (tid == 0) {
+                a.inf_task[ni] = t;
+                a.inf_pos[ni] = nc;
+                a.out_node[t] = -1;
+            }
+            ++ni;
+        } else {
+            if ((gn & (SCAN_THREADS - 1u)) == tid) {
+                const u32 nd = gn, w = nd >> 6;
+                const u64 bit = 1ull << (nd & 63);
+                if (r.cpu) a.cpu[nd] -= r.cpu;
+                if (r.mem) a.mem[nd] -= r.mem;
+                if (gset)
+                    for (u32 g = a.gs_off[gset]; g < a.gs_off[gset + 1]; ++g) a.gcnt[(size_t)a.rg_kind[a.gs_row[g]] * a.gstride + nd] -= a.rg_val[a.gs_row[g]];   // Claim
+                if (r.flags & RT_PORTS)
+                    for (u32 q = a.pset_off[r.pset]; q < a.pset_off[r.pset + 1]; ++q) wv::g_or64(a.portmap + (size_t)a.pset_ids[q] * Wn + w, bit);
+                if (!(r.flags & RT_UNCOUNTED)) {
+                    a.total[nd] += 1;
+                    const u32 hi = (u32)(gk >> 32) + 1u;   // (the pick's key carries its key half)
+                    u32 entry = s.emat[(size_t)r.svc * N + nd];
+                    if ((hi & 0xFFFFFFu) == 0) a.blk->error = ERR_GROUP_RANGE;
+                    s.hmat[(size_t)r.svc * N + nd] = hi;
+                    if (entry == LIST_EMPTY) {
+                        wv::g_or64(a.X + (size_t)r.svc * a.xs + w, bit);
+                        a.list_node[r.slot] = nd;
+                        a.list_svc[r.slot] = 1;
+                        a.list_fail[r.slot] = 0;
+                        s.emat[(size_t)r.svc * N + nd] = r.slot;
+                    } else
+                        a.list_svc[entry] = hi & 0xFFFFFFu;   // (the entry's count is the key half's low 24 bits)
+                    // (the plain instance corrects the next task's copy of this cell here. There is no copy: this thread stores the
+                    // cell and loads it again, in the next task's loop over its nodes, in program order.)
+                }
+                const int32_t prev = a.last[nd];
+                a.log_node[nc] = nd;
+                a.log_task[nc] = t;
+                a.log_prev[nc] = prev;
+                a.last[nd] = (int32_t)nc;
+                a.out_node[t] = (int32_t)nd;
+            }
+            ++nc;
+        }
+        // (no third barrier: a node's row and its matrix cells are read and written by its owner only; the per-tree words alternate)
+    }
+    if (tid == 0) {
+        a.ctl->ncommit = nc;
+        a.ctl->ninf = ni;
+        a.blk->pos = t;   // (s.j1, or the task the segment stopped in front of)
+    }
+}
+#endif   // SWP_SCAN_SPREAD_KERNEL
+
 }  // namespace swpdev

@@ -27,9 +27,17 @@ profiles/oneoff_spread.json).
                   preparation's share — first probe, cut, second probe — from the engine's own SWP_DEBUG_PREPARE line.
                   e.g. --pool --riders --out profiles/oneoff_spread_cut.json
 
+  --wide        the WIDE form instead of (a) - (c) (csrc/swp_scan_spread.hpp k_scan_spread_wide, SWP_SPREAD_WIDE=1): --wide-nodes nodes
+                  (default 10 000) over --zones zones, --tasks UNCONSTRAINED one-off tasks with `spread=node.labels.zone` — each task's own
+                  class row is the whole nodeSet. SWP_SCHED_ONEOFF_SPREAD=1 on both sides; SWP_SPREAD_WIDE unset (what the parent commit
+                  does with this tick: the batch is refused at its preparation, then a group call per task — the baseline) against
+                  SWP_SPREAD_WIDE=1, --runs fresh schedulers each, alternating. Both sides must decide every task alike.
+                  e.g. --wide --out profiles/oneoff_spread_wide.json
+
 usage: python tools/bench_oneoff_spread.py [--tasks 20000] [--services 200] [--nodes 1000] [--zones 5] [--runs 3] [--out FILE]
        python tools/bench_oneoff_spread.py --pool [--pool-nodes 10000] [--pool-every 10] [--tasks 20000] [--services 200] [--runs 3] [--out FILE]
-       python tools/bench_oneoff_spread.py --pool --riders [--riders-every 50] [--riders-count 10] [--runs 3] [--out FILE]"""
+       python tools/bench_oneoff_spread.py --pool --riders [--riders-every 50] [--riders-count 10] [--runs 3] [--out FILE]
+       python tools/bench_oneoff_spread.py --wide [--wide-nodes 10000] [--tasks 20000] [--services 200] [--runs 3] [--out FILE]"""
 import argparse
 import json
 import os
@@ -47,6 +55,7 @@ from swarmkit_amd import host as swhost  # noqa: E402
 
 READY, RUNNING, PENDING, ASSIGNED = 2, 512, 64, 192
 KNOB = "SWP_SCHED_ONEOFF_SPREAD"
+WIDE = "SWP_SPREAD_WIDE"   # (read once, when the engine is created)
 
 
 def node_doc(i, zones):
@@ -219,6 +228,50 @@ def pool_main(a):
             f.write(json.dumps(out, indent=1) + "\n")
 
 
+def wide_main(a):
+    os.environ["SWP_HOST"] = "cxx"
+    os.environ.pop(WIDE, None)
+    one_tick(argparse.Namespace(nodes=64, zones=a.zones, services=4, tasks=64), True)   # warm: modules, pools
+    shape = argparse.Namespace(nodes=a.wide_nodes, zones=a.zones, services=a.services, tasks=a.tasks)
+
+    def side(wide, profile=False):
+        if wide:
+            os.environ[WIDE] = "1"
+        else:
+            os.environ.pop(WIDE, None)
+        try:
+            return one_tick(shape, True, profile)
+        finally:
+            os.environ.pop(WIDE, None)
+
+    off, on, want, st_on, st_off = [], [], None, None, None
+    for r in range(a.runs):
+        for wide in ((False, True) if r % 2 == 0 else (True, False)):
+            ms, dec, st = side(wide)
+            (on if wide else off).append(ms)
+            if want is None:
+                want = dec
+            assert dec == want, "the two sides decide the tick differently"
+            if wide:
+                assert st["scan_tasks"] == a.tasks and st["scan_launches"] == 1, st
+                st_on = st
+            else:
+                assert st["scan_tasks"] == 0, st   # (refused at the preparation: no spread segment ran)
+                st_off = st
+    ms, _, st = side(True, profile=True)
+    eng = {"tick_ms_with_profile": round(ms, 3), "segment_ms": round(st["ms_scan"], 3), "batch_ms_total": round(st["ms_total"], 3),
+           "segment_us_per_task": round(st["ms_scan"] * 1e3 / a.tasks, 3)}
+    out = {"tool": "bench_oneoff_spread --wide", "tasks": a.tasks, "services": a.services, "nodes": a.wide_nodes, "zones": a.zones, "runs": a.runs,
+           "placed": sum(1 for v in want.values() if v),
+           "counters": {"wide_unset_parent_path": {k: st_off[k] for k in ("batches", "scan_launches", "scan_tasks")}, "wide_on": {k: st_on[k] for k in ("batches", "scan_launches", "scan_tasks")}},
+           "tick_ms": {"wide_unset_parent_path": summary(off), "wide_on": summary(on), "unset_over_on_median": round(statistics.median(off) / statistics.median(on), 2)},
+           "engine_wide_on": eng}
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
 def summary(v):
     return {"runs": [round(x, 3) for x in v], "min": round(min(v), 3), "median": round(statistics.median(v), 3), "max": round(max(v), 3), "spread": round(max(v) - min(v), 3)}
 
@@ -255,7 +308,11 @@ def main():
     ap.add_argument("--riders", action="store_true", help="with --pool: unconstrained plain one-off tasks between runs of the pooled spread tasks (the segment is cut)")
     ap.add_argument("--riders-every", type=int, default=50)
     ap.add_argument("--riders-count", type=int, default=10)
+    ap.add_argument("--wide", action="store_true", help="the wide form: unconstrained spread tasks on a cluster beyond 4 096 nodes, SWP_SPREAD_WIDE=1 against unset")
+    ap.add_argument("--wide-nodes", type=int, default=10_000)
     a = ap.parse_args()
+    if a.wide:
+        return wide_main(a)
     if a.pool:
         return pool_main(a)
     os.environ["SWP_HOST"] = "cxx"
